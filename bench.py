@@ -4,20 +4,28 @@
 Headline (BASELINE.json configs[1]): 1,048,576 pre-generated 1024-B UDP MgenMsg records
 (flow = 1 + i mod 64, per-flow seq, tx = 1.7e9 s + i us, dst 127.0.0.1/5000, checksum on:
 flags 0x0C), packed on the GPU by mgenx_pack_batch, resident in HBM.  One step = one
-mgenx_unpack_batch over the whole batch (CRC-validating decode into 32-B mgenx_rec rows; the
-SoA column layout is timed beside it in extra.columns_layout).
+mgenx_unpack_batch over the whole batch (CRC-validating decode into 32-B mgenx_rec rows; with
+--full the SoA column layout is timed beside it in extra.columns_layout).
 
 Algorithmic bytes per step: read 1,073,741,824 B of records + write
 N x 32 B rows = 1,107,296,256 B.  The metric names pack and unpack: `value` is the unpack
 (the receive path), `extra.pack_unpack_config2` the two together.  value = whole-job GB/s over all ranks (weak
 scaling: each rank owns its own 1M-record slab; no data-path collective).
 
-Extras (same JSON line, "extra"): header-only decode, pack (config 2), config 3 (mixed-size
+A plain run does only what the headline needs: it builds the batch, warms up, times the
+K steps and prints the result line (`value`, `ms_per_step` = wall-clock milliseconds per
+timed step).  `--dump-outputs DIR` also writes the rows the last timed step produced
+(dump_outputs below).
+
+`--full` adds, in the same JSON line: the correctness gate on the freshly packed slab, the
+per-launch kernel time and the roofline figures, the "extra" block -- header-only decode,
+pack (config 2), config 3 (mixed-size
 pack + unpack with DATA payload), config 4 (per-flow analytics + the RCCL all-reduce of the
 per-flow counters across ranks), config 5 (TCP stream scan + TCP-rule unpack), and the
-PCIe-inclusive rate (pinned host slab -> H2D -> unpack -> columns D2H).
+PCIe-inclusive rate (pinned host slab -> H2D -> unpack -> columns D2H) -- and the CPU
+baseline.  `--no-extras` / `--no-cpu-baseline` trim a `--full` run.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 (N > 1: launched by torch.distributed.run, one rank per GPU.)
 """
 import argparse
@@ -602,9 +610,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the rows of the last timed step as DIR/<field>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also: correctness gate, kernel time + roofline, extras, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extra configs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # MGENX_BENCH_REHEARSE=1: the N-rank protocol on however many GPUs are visible (ranks
     # share them), torch.distributed over gloo, the RCCL counter merge replaced by a gloo
@@ -639,7 +653,7 @@ def main():
     # collectives of host-side values: device tensors over RCCL, CPU tensors over gloo
     cdev = torch.device("cpu") if rehearse else dev
 
-    from mgen_amd import OPT_SKIP_CRC, PACK_CHECKSUM, UNPACK_K_FIXED_RING, Engine, to_device
+    from mgen_amd import PACK_CHECKSUM, Engine, to_device
     from mgen_amd.workloads import udp_fixed
 
     eng = Engine(local)
@@ -679,15 +693,13 @@ def main():
         want = torch.arange(N_REC, device=dev, dtype=torch.int32) // 64
         return int((err != 0).sum()) == 0 and bool(torch.equal(seq, want))
 
-    # correctness gate before timing
-    step()
-    torch.cuda.synchronize()
-    if not rows_ok() or int((out_len != REC).sum()):
-        raise RuntimeError("unpack found bad records in a freshly packed slab")
+    if args.full:
+        # correctness gate before timing
+        step()
+        torch.cuda.synchronize()
+        if not rows_ok() or int((out_len != REC).sum()):
+            raise RuntimeError("unpack found bad records in a freshly packed slab")
 
-    which = eng.last_unpack_kernel()      # the kernel the timed steps launch
-    kernel_name = {UNPACK_K_FIXED_RING: "mgenx::unpack_fixed_ring_kernel<16, 4, 16>"}.get(
-        which, f"UNPACK_K_{which} (not the ring kernel)")
     for _ in range(args.warmup):
         step()
     if world > 1:
@@ -705,6 +717,76 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows)
+    roofline = extra = None
+    if args.full:
+        roofline, extra = full_measurements(torch, dist, args, eng, dev, local, world, rank,
+                                            rehearse, slab, step, do_pack, rows_ok)
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * ALGO_BYTES * args.steps / elapsed / 1e9
+    if rank == 0:
+        line = {
+            "metric": "device-resident MgenMsg pack+unpack GB/s and Mmsg/s at 1/2/4/8 MI355X",
+            "value": round(value, 2),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic (GPU-packed MgenMsg records, reference Pack semantics)",
+            "config": {"workload": "udp_unpack_crc_1M_x_1024B",
+                       "value_is": "unpack + receive CRC check of config 2 (pack: extra.pack_*)",
+                       "records_per_gpu": N_REC,
+                       "record_bytes": REC, "checksum": True, "output": "mgenx_rec rows (32 B)",
+                       "algorithmic_bytes_per_step_per_gpu": ALGO_BYTES,
+                       "parallelism": f"flow-sharded x{world} (independent slabs)",
+                       **({"rehearsal": "ranks share GPUs over gloo: numbers invalid"}
+                          if rehearse else {})},
+            "mmsg_per_s": round(world * N_REC * args.steps / elapsed / 1e6, 2),
+        }
+        if args.full:
+            line["roofline"] = roofline
+            line["extra"] = extra
+            if not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline()
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, rows):
+    """--dump-outputs: what a caller of the timed step receives -- the mgenx_rec rows of the
+    last timed step -- as out_dir/<field>.npy, one array per field of the 32-B row (32-bit
+    fields as float64, narrower ones as float32: every value exact).  All 1,048,576 rows
+    would be 80 MB that way, so a fixed seeded sample of half of them (sorted record
+    indices, the first and the last row among them) is written: 40 MB."""
+    from mgen_amd import REC_DTYPE
+    rec = rows.cpu().numpy().view(REC_DTYPE)
+    n = rec.size
+    pick = np.random.default_rng(20240611).choice(n, n // 2, replace=False)
+    pick[:2] = 0, n - 1
+    rec = rec[np.unique(pick)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name in REC_DTYPE.names:
+        wide = REC_DTYPE[name].itemsize > 2
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                rec[name].astype(np.float64 if wide else np.float32))
+
+
+def full_measurements(torch, dist, args, eng, dev, local, world, rank, rehearse, slab, step,
+                      do_pack, rows_ok):
+    """--full: everything beside the headline, after the timed steps: the per-launch kernel
+    time and the roofline block, then the `extra` block.  Returns (roofline, extra)."""
+    from mgen_amd import OPT_SKIP_CRC, UNPACK_K_FIXED_RING, Engine
+    which = eng.last_unpack_kernel()      # the kernel the timed steps launched
+    kernel_name = {UNPACK_K_FIXED_RING: "mgenx::unpack_fixed_ring_kernel<16, 4, 16>"}.get(
+        which, f"UNPACK_K_{which} (not the ring kernel)")
     # per-launch kernel duration with HIP events on the launch stream
     n_ev = max(10, min(args.steps, 50))
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -726,7 +808,7 @@ def main():
     col_ms = timed(torch, lambda: eng.unpack(slab, N_REC, stride=REC, fixed_len=REC,
                                              cols=ccols), reps=20)
     assert int((ccols["err"] != 0).sum()) == 0
-    # memory-system probes on this box: the unpack's read pattern alone, and with 512-B
+    # memory-system probes on this GPU: the unpack's read pattern alone, and with 512-B
     # row stores per 16-KiB group (mgenx_diag_group_rw)
     probe_out = torch.empty(N_REC * 32, dtype=torch.uint8, device=dev)
     probe = Engine(local, diag=True)   # libmgenx_diag.so: the memory-pattern probes
@@ -770,45 +852,14 @@ def main():
             guard("convert_binary_log_1M", lambda: extra_convert(torch, eng, dev, slab))
 
     traffic_b, traffic_src = load_traffic()
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * ALGO_BYTES * args.steps / elapsed / 1e9
     achieved = ALGO_BYTES / (kern_ms * 1e-3) / 1e9
-    if rank == 0:
-        line = {
-            "metric": "device-resident MgenMsg pack+unpack GB/s and Mmsg/s at 1/2/4/8 MI355X",
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (GPU-packed MgenMsg records, reference Pack semantics)",
-            "config": {"workload": "udp_unpack_crc_1M_x_1024B",
-                       "value_is": "unpack + receive CRC check of config 2 (pack: extra.pack_*)",
-                       "records_per_gpu": N_REC,
-                       "record_bytes": REC, "checksum": True, "output": "mgenx_rec rows (32 B)",
-                       "algorithmic_bytes_per_step_per_gpu": ALGO_BYTES,
-                       "parallelism": f"flow-sharded x{world} (independent slabs)",
-                       **({"rehearsal": "ranks share GPUs over gloo: numbers invalid"}
-                          if rehearse else {})},
-            "mmsg_per_s": round(world * N_REC * args.steps / elapsed / 1e6, 2),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBPS,
-                         "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBPS, 4),
-                         "traffic": traffic_b,
-                         "traffic_source": traffic_src and os.path.relpath(traffic_src, ROOT),
-                         "kernel": kernel_name,
-                         "kernel_ms": round(kern_ms, 4)},
-            "extra": extra,
-        }
-        if not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBPS,
+                "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBPS, 4),
+                "traffic": traffic_b,
+                "traffic_source": traffic_src and os.path.relpath(traffic_src, ROOT),
+                "kernel": kernel_name,
+                "kernel_ms": round(kern_ms, 4)}
+    return roofline, extra
 
 
 if __name__ == "__main__":

@@ -21,8 +21,8 @@ step() {  # step <name> <timeout-seconds> <cmd...>
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { cat $OUT/build.log; exit 1; }
 step pytest_gpu 600 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS:-}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps ${STEPS:-50} --warmup ${WARMUP:-10}
+step bench 600 python bench.py --full --steps ${STEPS:-50} --warmup ${WARMUP:-10}
 if [ "${PROFILE:-1}" = "1" ]; then
-  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   find $OUT/prof -name "*stats*" | head
 fi

@@ -20,5 +20,5 @@ if [ "${SUITE:-1}" = "1" ]; then
   step suite 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  step bench 600 python -u bench.py --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-}
+  step bench 600 python -u bench.py --full --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-}
 fi

@@ -17,7 +17,7 @@ if [ -n "${TESTS:-}" ]; then
   step tests 600 python -u -m pytest $TESTS -m gpu -x -q --timeout 200 --timeout-method thread
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  step bench 600 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-}
+  step bench 600 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-}
 fi
 for c in ${TRACE:-}; do
   step trace_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/tr_$c -o tr \

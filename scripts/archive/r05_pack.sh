@@ -12,7 +12,7 @@ step() {  # step <name> <timeout> <cmd...>
   if [ $rc -ne 0 ]; then echo "STEP $name FAILED rc=$rc"; exit $rc; fi
 }
 step pack_tests 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_pack_layout.py tests/test_gpu_pack_msgs.py tests/test_gpu_tcp_tx.py -m gpu -x -q --timeout 120 --timeout-method thread
-step bench_nocpu 300 python -u bench.py --no-cpu-baseline
+step bench_nocpu 300 python -u bench.py --full --no-cpu-baseline
 python3 - <<'PY'
 import json
 l=[x for x in open("gpurun_out/bench_nocpu.log") if x.startswith("{")][-1]
