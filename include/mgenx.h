@@ -841,6 +841,89 @@ int mgenx_convert_binary_log(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t bu
                              uint32_t opts, char* dev_text, uint64_t text_cap,
                              uint64_t* dev_rec_pos, void* stream);
 
+/* ---- text log ingest: MGEN text log -> columns (the inverse of the text formatters) ----
+ * The lines `mgen output <file>`, pcap2mgen and ConvertBinaryLog write (doc/mgen.xml, "MGEN Log
+ * File Format"), read back into the columns mgenx_flow_lookup / mgenx_flow_reduce take.
+ * Line grammar ("text log ingest"):
+ *   <ts> SP+ <EVENT> (SP+ <key>'>'<value>)* SP* [CR] LF
+ * <ts> is "HH:MM:SS.uuuuuu" or "<sec>.uuuuuu", told apart per token.  RECV, RERR and SEND
+ * lines have their keys parsed (unknown keys are skipped); every other event gives its code
+ * and timestamp only.  An empty line is MGENX_EVENT_NONE with status OK.
+ *
+ * mgenx_text_index: line k = dev_text[dev_line_off[k], dev_line_off[k + 1]) including its
+ * LF; dev_n_lines[0] = the line count (a final non-empty piece without LF counts).
+ * dev_line_off holds cap + 1 entries and is written only when the count fits cap (the
+ * two-pass convention of mgenx_log_recv_text: read dev_n_lines[0] and call again).
+ * Asynchronous; the context keeps a workspace (about nbytes / 2048 bytes), so these calls run on
+ * one stream at a time per context. */
+#define MGENX_EVENT_NONE        0   /* LogEventType (include/mgenGlobals.h:36-56) */
+#define MGENX_EVENT_RECV        1
+#define MGENX_EVENT_RERR        2
+#define MGENX_EVENT_SEND        3
+#define MGENX_EVENT_LISTEN      4
+#define MGENX_EVENT_IGNORE      5
+#define MGENX_EVENT_JOIN        6
+#define MGENX_EVENT_LEAVE       7
+#define MGENX_EVENT_START       8
+#define MGENX_EVENT_STOP        9
+#define MGENX_EVENT_ON         10
+#define MGENX_EVENT_ACCEPT     11
+#define MGENX_EVENT_DISCONNECT 12
+#define MGENX_EVENT_CONNECT    13
+#define MGENX_EVENT_OFF        14
+#define MGENX_EVENT_SHUTDOWN   15
+#define MGENX_EVENT_RECONNECT  16
+#define MGENX_EVENT_REPORT     17   /* not a LogEventType: REPORT lines, classified only */
+#define MGENX_PARSE_OK         0
+#define MGENX_PARSE_MALFORMED  1
+#define MGENX_HAS_HOST   0x01       /* mgenx_logparse_out.present: optional keys on the line */
+#define MGENX_HAS_TTL    0x02
+#define MGENX_HAS_GPS    0x04
+#define MGENX_HAS_DATA   0x08
+#define MGENX_HAS_FLAGS  0x10
+#define MGENX_ERROR_NOT_RECV 0x20   /* cols.err of every line that is not an OK RECV / RERR */
+#define MGENX_PARSE_NO_DAYS  0x1    /* opts: legacy stamps stay times of day */
+
+int mgenx_text_index(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
+                     uint64_t* dev_line_off, uint64_t cap, uint64_t* dev_n_lines, void* stream);
+
+/* mgenx_log_parse_text: n lines -> one element per line in every array given.  A line is
+ * MGENX_PARSE_OK iff its timestamp parses, its event is known, every required key is there
+ * (RECV: proto flow seq src dst sent size; RERR: type src; SEND: proto flow seq srcPort dst
+ * size) and every known key's value is valid and fits its field; else MGENX_PARSE_MALFORMED,
+ * its other outputs unspecified.  Absent optional fields read 0 (ttl -1).
+ * cols.err: 0 for an OK RECV line, the RERR code (MGENX_ERROR_RERR_NONE for "none") for an OK
+ * RERR line, MGENX_ERROR_NOT_RECV for every other line -- so the columns go to
+ * mgenx_flow_lookup as they are (those lines map to MGENX_FLOW_NONE and mgenx_flow_reduce skips
+ * them).
+ * Legacy stamps hold the time of day only: rx_sec = day_base_sec + 86400 * wraps + tod, where
+ * wraps counts the OK legacy lines up to this one whose time of day lies more than 43200 s
+ * below that of the nearest earlier OK legacy line; a legacy sent> time is put on the day among
+ * {rx day - 1, rx day, rx day + 1} closest to the rx time (the earlier one on a tie).
+ * MGENX_PARSE_NO_DAYS leaves both as times of day.  Epoch stamps are taken as they are.
+ * The decoded data> bytes go to payload at payload_off[k] (n + 1 offsets), written only when
+ * the total fits payload_cap (two passes).  Asynchronous; per-context workspace (about 48
+ * bytes per line), shared with mgenx_text_index. */
+typedef struct {            /* every pointer optional unless noted; n elements each */
+    uint8_t*  event;        /* required: MGENX_EVENT_* */
+    uint8_t*  status;       /* required: MGENX_PARSE_OK / _MALFORMED */
+    uint8_t*  protocol;     /* MGENX_PROTO_*, 0 for any other proto> word */
+    uint16_t* present;      /* MGENX_HAS_HOST | _TTL | _GPS | _DATA | _FLAGS */
+    uint32_t* rx_sec; uint32_t* rx_usec;   /* the line's own timestamp */
+    mgenx_addr* src;        /* RECV / RERR src; SEND: type 0, port = srcPort */
+    int32_t*  ttl;          /* -1 when absent */
+    uint32_t* size;         /* the full size> value */
+    mgenx_cols cols;        /* flow_id seq_num tx_sec tx_usec msg_len (= min(size, 65535))
+                               dst_port flags err dst_type dst_len dst_addr4 dst_addr payload_len
+                               payload_type (0) gps_status lat_raw lon_raw alt host_*; the other
+                               members and rows are ignored */
+    uint8_t*  payload; uint64_t payload_cap; uint64_t* payload_off;
+} mgenx_logparse_out;
+
+int mgenx_log_parse_text(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
+                         const uint64_t* dev_line_off, uint32_t n, uint32_t opts,
+                         uint32_t day_base_sec, const mgenx_logparse_out* out, void* stream);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ----
  * One communicator per rank (one process per GPU): rank 0 calls mgenx_comm_unique_id and
  * hands the MGENX_COMM_ID_BYTES bytes to every rank (any out-of-band channel), then every

@@ -23,6 +23,9 @@ from ._abi import (  # noqa: F401
     LOG_SKIP_ERR, FLOW_NONE, DLT_EN10MB, DLT_LINUX_SLL, BinlogInfo, BINLOG_NO_RX, BINLOG_FLUSH,
     UNPACK_K_HEADER, UNPACK_K_GENERAL, UNPACK_K_VAR, UNPACK_K_FIXED, UNPACK_K_FIXED_RING,
     UNPACK_K_OTHER, UNPACK_K_LONG, UNPACKED_DTYPE,
+    EVENT_NONE, EVENT_RECV, EVENT_RERR, EVENT_SEND, EVENT_REPORT, PARSE_OK, PARSE_MALFORMED,
+    HAS_HOST, HAS_TTL, HAS_GPS, HAS_DATA, HAS_FLAGS, ERROR_RERR_NONE, ERROR_NOT_RECV,
+    PARSE_NO_DAYS, LOGPARSE_COLS, LogparseOut,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,7 +49,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_unpack_last_kernel", "mgenx_pcap_snap", "mgenx_flow_reduce_rows",
     "mgenx_worker_create", "mgenx_worker_destroy", "mgenx_worker_unpack", "mgenx_worker_crc32",
     "mgenx_worker_pack", "mgenx_worker_stop", "mgenx_worker_info", "mgenx_worker_recv",
-    "mgenx_worker_flow_update",
+    "mgenx_worker_flow_update", "mgenx_text_index", "mgenx_log_parse_text",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -109,6 +112,9 @@ def load(diag: bool = False):
     L.mgenx_pcap_snap.argtypes = [P, P, u64, u64, P, u32, u32, P, P, P, P]
     L.mgenx_binlog_index.argtypes = [P, u64, P, u64, ctypes.POINTER(BinlogInfo)]
     L.mgenx_convert_binary_log.argtypes = [P, P, u64, P, u32, u32, u32, P, u64, P, P]
+    L.mgenx_text_index.argtypes = [P, P, u64, P, u64, P, P]
+    L.mgenx_log_parse_text.argtypes = [P, P, u64, P, u32, u32, u32, ctypes.POINTER(LogparseOut),
+                                       P]
     if diag:
         L.mgenx_set_tuning.argtypes = [P, i32, i32]
         L.mgenx_diag_stream_read.argtypes = [P, P, u64, P, i32, P]
@@ -306,6 +312,71 @@ class Engine:
                 return out[:total], pos
             cap = total
         raise MgenxError("mgenx_log_recv_binary: output did not fit")
+
+    # ------------------------------------------------------------ text log ingest
+    def text_index(self, text, nbytes=None):
+        """Line offsets of a text log on the device (mgenx_text_index): text is a uint8 tensor;
+        returns (line_off int64 tensor of n_lines + 1, n_lines).  Line k is
+        text[line_off[k]:line_off[k + 1]], its LF included."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        nbytes = text.numel() if nbytes is None else nbytes
+        n_lines = torch.zeros(1, dtype=torch.int64, device=dev)
+        cap = max(1, nbytes // 64)
+        for _ in range(2):
+            line_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            rc = self.lib.mgenx_text_index(self.ctx, _ptr(text), nbytes, _ptr(line_off), cap,
+                                           _ptr(n_lines), _stream(self.device))
+            self._check(rc, "mgenx_text_index")
+            n = int(n_lines.item())
+            if n <= cap:
+                return line_off[:n + 1], n
+            cap = n
+        raise MgenxError("mgenx_text_index: line offsets did not fit")
+
+    def log_parse_text(self, text, line_off, n, *, opts=0, day_base=0, payload=False,
+                       nbytes=None):
+        """Parse n text log lines into columns (mgenx_log_parse_text).  Returns a dict of
+        tensors: event, status, protocol, present, rx_sec, rx_usec, src (n x 20), ttl, size,
+        the mgenx_cols columns (core + extended, ready for flow_lookup / flow_reduce) and, with
+        payload=True, payload (the decoded data> bytes) and payload_off (n + 1)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        nbytes = text.numel() if nbytes is None else nbytes
+        m = max(n, 1)
+        out = {name: torch.zeros(m * w, dtype=getattr(torch, dt), device=dev)
+               for name, dt, w in LOGPARSE_COLS}
+        cols = {name: torch.zeros(m * w, dtype=getattr(torch, dt), device=dev)
+                for name, dt, w in COLS_CORE + COLS_EXT}
+        s = LogparseOut()
+        for name, _, _ in LOGPARSE_COLS:
+            setattr(s, name, out[name].data_ptr())
+        s.cols = self._cols_struct(cols)
+        if payload:
+            out["payload_off"] = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            s.payload_off = out["payload_off"].data_ptr()
+        cap = 0
+        for _ in range(2):
+            if payload:
+                out["payload"] = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+                s.payload, s.payload_cap = out["payload"].data_ptr(), cap
+            rc = self.lib.mgenx_log_parse_text(self.ctx, _ptr(text), nbytes, _ptr(line_off), n,
+                                               opts, day_base, ctypes.byref(s),
+                                               _stream(self.device))
+            self._check(rc, "mgenx_log_parse_text")
+            if not payload:
+                break
+            total = int(out["payload_off"][n].item())
+            if total <= cap:
+                out["payload"] = out["payload"][:total]
+                break
+            cap = total
+        for name, _, w in LOGPARSE_COLS:
+            out[name] = out[name][:n * w]
+        # mgenx_cols members the parser does not write (hdr_len, the u32 payload_off) stay out
+        out.update({k: v[:n * (16 if k in ("dst_addr", "host_addr") else 1)]
+                    for k, v in cols.items() if k not in ("hdr_len", "payload_off")})
+        return out
 
     # ------------------------------------------------------------ pack
     def pack_prepare(self, tmpl, n_tmpl, pool, tmpl_crc):
@@ -811,6 +882,45 @@ def convert_binary_log(log, log_rx=True, flush=False, opts=0, device=0) -> tuple
         text, _ = eng.convert_binary_log(buf, ro, n, flags, opts)
         return text.cpu().numpy().tobytes(), info
     finally:
+        eng.close()
+
+
+def analyze_text_log(log_bytes, window=1.0, day_base=0, device=0) -> tuple:
+    """Per-flow receive analytics of an MGEN text log, on the GPU: line index -> parse ->
+    FindFlow -> MgenAnalytic::Update -> counters.  Returns (keys, counters, n_lines,
+    n_malformed): numpy arrays of REPORT_KEY_DTYPE and FLOW_COUNTERS_DTYPE, one element per
+    flow in the order of each flow's first RECV line.  The keys' protocol is that of the
+    first OK RECV line."""
+    import torch
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
+        line_off, n = eng.text_index(text)
+        empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_COUNTERS_DTYPE))
+        if n == 0:
+            return empty + (0, 0)
+        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+        n_bad = int((p["status"] != PARSE_OK).sum().item())
+        table = eng.flow_table(max(n, 16))
+        flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
+        nf = int(n_flows.item())
+        if nf == 0:
+            return empty + (n, n_bad)
+        flows = eng.flow_init(nf, window)
+        eng.flow_reduce(flows, nf, flow_idx, p["seq_num"], p["tx_sec"], p["tx_usec"],
+                        p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+        recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
+        proto = int(p["protocol"][recv][0].item())
+        keys = eng.flow_keys(table, nf, protocol=proto)
+        counters = eng.flow_export(flows, nf)
+        torch.cuda.synchronize(device)
+        return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
+                counters.cpu().numpy().view(FLOW_COUNTERS_DTYPE)[:nf].copy(), n, n_bad)
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
         eng.close()
 
 

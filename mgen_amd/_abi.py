@@ -184,3 +184,26 @@ UNPACKED_DTYPE = np.dtype([
     ("dst_addr", "u1", 16), ("host_addr", "u1", 16),
 ], align=True)
 assert UNPACKED_DTYPE.itemsize == 88
+
+
+# ---- text log ingest (mgenx_text_index / mgenx_log_parse_text) ----
+(EVENT_NONE, EVENT_RECV, EVENT_RERR, EVENT_SEND, EVENT_LISTEN, EVENT_IGNORE, EVENT_JOIN,
+ EVENT_LEAVE, EVENT_START, EVENT_STOP, EVENT_ON, EVENT_ACCEPT, EVENT_DISCONNECT, EVENT_CONNECT,
+ EVENT_OFF, EVENT_SHUTDOWN, EVENT_RECONNECT, EVENT_REPORT) = range(18)
+PARSE_OK, PARSE_MALFORMED = 0, 1
+HAS_HOST, HAS_TTL, HAS_GPS, HAS_DATA, HAS_FLAGS = 0x01, 0x02, 0x04, 0x08, 0x10
+ERROR_RERR_NONE = 0x40    # MGENX_ERROR_RERR_NONE
+ERROR_NOT_RECV = 0x20     # MGENX_ERROR_NOT_RECV
+PARSE_NO_DAYS = 0x1       # MGENX_PARSE_NO_DAYS
+# the per-line outputs besides cols: (name, torch dtype name, elements per line)
+LOGPARSE_COLS = (
+    ("event", "uint8", 1), ("status", "uint8", 1), ("protocol", "uint8", 1),
+    ("present", "int16", 1), ("rx_sec", "int32", 1), ("rx_usec", "int32", 1),
+    ("src", "uint8", 20), ("ttl", "int32", 1), ("size", "int32", 1),
+)
+
+
+class LogparseOut(ctypes.Structure):   # mgenx_logparse_out
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in LOGPARSE_COLS] + \
+        [("cols", MgenxCols), ("payload", ctypes.c_void_p), ("payload_cap", ctypes.c_uint64),
+         ("payload_off", ctypes.c_void_p)]

@@ -120,6 +120,16 @@ extern "C" int mgenx_binlog_lines_exec(void* wsp, const uint8_t* buf, const uint
                                        uint64_t* line_off, hipStream_t stream, char* err,
                                        size_t errn);
 
+extern "C" size_t mgenx_text_index_ws(uint64_t nbytes);
+extern "C" int mgenx_text_index_run(void* ws, const uint8_t* text, uint64_t nbytes,
+                                    uint64_t* line_off, uint64_t cap, uint64_t* n_lines,
+                                    hipStream_t stream, char* err, size_t errn);
+extern "C" size_t mgenx_log_parse_ws(uint32_t n);
+extern "C" int mgenx_log_parse_run(void* ws, const uint8_t* text, uint64_t nbytes,
+                                   const uint64_t* line_off, uint32_t n, uint32_t opts,
+                                   uint32_t day_base, const mgenx_logparse_out* out,
+                                   hipStream_t stream, char* err, size_t errn);
+
 // a device buffer that grows on demand (the composite calls' intermediate arrays)
 struct mgenx_grow {
   void* p = nullptr;
@@ -171,6 +181,7 @@ struct mgenx_ctx {
   int pack_variant = 0;
   mgenx_grow bl[5];                // mgenx_convert_binary_log: records, lines, pairs, report text
   mgenx_grow snap;                 // mgenx_pcap_snap: per-packet sizes + scan scratch
+  mgenx_grow lp;                   // mgenx_text_index / mgenx_log_parse_text: per-line scratch
   bool rand_ready = false;
   uint32_t rand_time = 0;
   std::vector<mgenx_worker*> workers;  // live workers on this context (stopped by ctx destroy)
@@ -364,6 +375,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   mgenx::host_free(c->tcp_host);
   for (mgenx_grow& g : c->bl) g.release();
   c->snap.release();
+  c->lp.release();
   for (void* p : ps) mgenx::dev_free(p);
   delete c;
   return MGENX_OK;
@@ -1651,6 +1663,41 @@ int mgenx_convert_binary_log(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t bu
     n_src = 2;
   }
   return mgenx_text_interleave(ctx, srcs, n_src, n, dev_text, text_cap, dev_rec_pos, stream);
+}
+
+int mgenx_text_index(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
+                     uint64_t* dev_line_off, uint64_t cap, uint64_t* dev_n_lines, void* stream) {
+  if (!ctx || !dev_n_lines || (nbytes && !dev_text) || (cap && !dev_line_off) ||
+      nbytes > (1ull << 44))
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  void* ws = nullptr;
+  if (nbytes) {
+    ws = ctx->lp.get(mgenx_text_index_ws(nbytes));
+    if (!ws) return set_err(ctx, hipErrorOutOfMemory, "text_index workspace");
+  }
+  return mgenx_text_index_run(ws, (const uint8_t*)dev_text, nbytes, dev_line_off, cap, dev_n_lines,
+                              (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_log_parse_text(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
+                         const uint64_t* dev_line_off, uint32_t n, uint32_t opts,
+                         uint32_t day_base_sec, const mgenx_logparse_out* out, void* stream) {
+  if (!ctx || !out || !out->event || !out->status || (n && (!dev_line_off || !dev_text)) ||
+      (out->payload_cap && !out->payload) || (out->payload && !out->payload_off) ||
+      (opts & ~(uint32_t)MGENX_PARSE_NO_DAYS) || n > 0x7FFFFFFEu)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (n == 0) {
+    if (out->payload_off &&
+        hipMemsetAsync(out->payload_off, 0, 8, (hipStream_t)stream) != hipSuccess)
+      return set_err(ctx, hipGetLastError(), "log_parse_text");
+    return MGENX_OK;
+  }
+  void* ws = ctx->lp.get(mgenx_log_parse_ws(n));
+  if (!ws) return set_err(ctx, hipErrorOutOfMemory, "log_parse_text workspace");
+  return mgenx_log_parse_run(ws, (const uint8_t*)dev_text, nbytes, dev_line_off, n, opts,
+                             day_base_sec, out, (hipStream_t)stream, ctx->err, sizeof(ctx->err));
 }
 
 }  // extern "C"
