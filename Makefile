@@ -9,14 +9,15 @@ NAMES := mgenx_api mgenx_unpack mgenx_pack mgenx_scan mgenx_analytic mgenx_log m
          mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_flowsm.hpp \
-       mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp
+       mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))
 DOBJ := $(addprefix build/diag/,$(addsuffix .o,$(NAMES)))
 LIBS := -L/opt/rocm/lib -lrccl -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
 
 all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundtrip \
      tests/cpp/loopback tests/cpp/compat_shapes tests/cpp/compat_shapes_pl tests/cpp/shim_latency \
-     tests/cpp/shard_scan tools/pcap2mgen tests/cpp/logparse_host
+     tests/cpp/shard_scan tools/pcap2mgen tests/cpp/logparse_host \
+     tests/cpp/pcapng_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -77,6 +78,13 @@ tools/pcap2mgen: tools/pcap2mgen.cpp include/mgenx_pcap.hpp include/mgenx.hpp in
 # the text log line parser (mgenx_logparse.hpp) as a stand-alone host program under the address
 # and undefined-behaviour sanitizers (tests/test_logparse_cpu.py); no HIP, no GPU
 tests/cpp/logparse_host: tests/cpp/logparse_host.cpp mgen_amd/csrc/mgenx_logparse.hpp include/mgenx.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Iinclude $< -o $@
+
+# the pcapng block walk (mgenx_pcapng.hpp) as a stand-alone host program under the address and
+# undefined-behaviour sanitizers: every prefix and single-field mutations of a capture
+# (tests/test_pcapng_cpu.py); no HIP, no GPU
+tests/cpp/pcapng_host: tests/cpp/pcapng_host.cpp mgen_amd/csrc/mgenx_pcapng.hpp include/mgenx.h
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Iinclude $< -o $@
 

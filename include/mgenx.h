@@ -798,6 +798,80 @@ int mgenx_pcap_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint6
                     const uint64_t* dev_pkt_off, uint32_t n, uint32_t flags, uint8_t* dev_status,
                     uint64_t* dev_udp_off, uint32_t* dev_udp_len, void* stream);
 
+/* ---- pcap2mgen: pcapng captures (what Wireshark, dumpcap and tshark write) ----
+ * The reference opens its input with pcap_fopen_offline (pcap2mgen.cpp:323) and libpcap reads
+ * pcapng there as it reads pcap.  libpcap is not part of the reference tree, so this layer
+ * restates its pcapng reader (parity unpinned, like the protolib packet classes); the walk
+ * rules are the contract and are listed in DESIGN.md 4.10 and mgen_amd/csrc/mgenx_pcapng.hpp.
+ * mgenx_pcapng_index (HOST memory, no device work) walks the blocks of a file image: Section
+ * Header (the section's byte order), Interface Description (link type, snaplen, if_tsresol,
+ * if_tsoffset), Enhanced / obsolete / Simple Packet blocks; every other block is skipped.
+ * The offsets of the first `cap` packet blocks go to pkt_off and each packet's row in the
+ * interface table to pkt_if; the first `if_cap` interfaces go to ifaces (rows are appended
+ * across sections).  The counts in info are always complete, so a first call with cap =
+ * if_cap = 0 sizes the arrays.  Returns MGENX_EINVAL for a buffer that does not start with a
+ * version-1 Section Header Block.  Otherwise info->status says how the walk ended; a stop
+ * keeps every packet before it (the reference loop ends when pcap_next returns NULL) and
+ * info->consumed is the offset of the block that stopped it:
+ *   _TRUNCATED the file ends inside a block
+ *   _BLOCK     a malformed block: a length below the type's minimum or not a multiple of 4,
+ *              a trailing length that differs from the leading one, an IDB option past its block
+ *   _SECTION   a later section of another byte order, a bad magic or a major version != 1
+ *   _LINKTYPE  an IDB of another link type than the file's first (pcap_datalink is one value)
+ *   _NO_IFACE  a packet on an interface its section has not described (an SPB: interface 0)
+ *   _TSRESOL   if_tsresol beyond 10^-19 / 2^-63, a wrong length of if_tsresol (1) or
+ *              if_tsoffset (8), or either option given twice
+ *   _CAPLEN    a captured length larger than the block's room for data
+ * mgenx_pcapng_parse (device, one lane per packet) reads each packet block (EPB / OPB / SPB),
+ * converts its 64-bit time stamp with its interface's resolution and offset -- uint64
+ * arithmetic that wraps, as libpcap's: sec = t / R + if_tsoffset, usec from t % R scaled to
+ * microseconds -- and runs the frame walk of mgenx_pcap_parse over the packet data.  Outputs
+ * as mgenx_pcap_parse, plus each packet's data offset and captured length (for the snap
+ * step).  A packet whose block head or data does not lie inside buf_bytes, whose pkt_if is not
+ * below n_ifaces or whose block is not a packet block gets MGENX_PCAP_OOB.
+ * mgenx_pcapng_snap is mgenx_pcap_snap for these packets. */
+#define MGENX_PCAP_NG 0x4            /* info.flags: offsets are pcapng packet blocks */
+#define MGENX_PCAPNG_OK        0
+#define MGENX_PCAPNG_TRUNCATED 1
+#define MGENX_PCAPNG_BLOCK     2
+#define MGENX_PCAPNG_SECTION   3
+#define MGENX_PCAPNG_LINKTYPE  4
+#define MGENX_PCAPNG_NO_IFACE  5
+#define MGENX_PCAPNG_TSRESOL   6
+#define MGENX_PCAPNG_CAPLEN    7
+typedef struct {
+    uint64_t ts_units;    /* time stamp units per second: 10^k or 2^k */
+    int64_t  ts_offset;   /* if_tsoffset (seconds) */
+    uint32_t snaplen;     /* 0 = no limit */
+    uint8_t  ts_binary;   /* ts_units is a power of two */
+    uint8_t  rsv[3];
+} mgenx_pcapng_if;        /* 24 bytes */
+typedef struct {
+    uint32_t link_type;   /* the first IDB's */
+    uint32_t flags;       /* MGENX_PCAP_NG | MGENX_PCAP_SWAPPED */
+    uint32_t snaplen;     /* the first IDB's */
+    int32_t  status;      /* MGENX_PCAPNG_* */
+    uint64_t n_records;   /* packet blocks found (only the first cap are written) */
+    uint64_t consumed;    /* bytes of whole blocks walked */
+    uint64_t snap_bytes;  /* as mgenx_pcap_info */
+    uint32_t n_ifaces;    /* interface rows (only the first if_cap are written) */
+    uint32_t n_sections;
+} mgenx_pcapng_info;
+int mgenx_pcapng_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off, uint32_t* pkt_if,
+                       uint64_t cap, mgenx_pcapng_if* ifaces, uint32_t if_cap,
+                       mgenx_pcapng_info* info);
+int mgenx_pcapng_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                       const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if, uint32_t n,
+                       const mgenx_pcapng_if* dev_ifaces, uint32_t n_ifaces, uint32_t link_type,
+                       uint32_t flags, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                       mgenx_addr* dev_src, int32_t* dev_ttl, uint32_t* dev_rx_sec,
+                       uint32_t* dev_rx_usec, uint8_t* dev_status, uint64_t* dev_data_off,
+                       uint32_t* dev_cap_len, void* stream);
+int mgenx_pcapng_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                      const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      void* stream);
+
 /* ---- MgenMsg::ConvertBinaryLog: binary log -> text log (src/common/mgenMsg.cpp:1417-1900) --
  * mgenx_binlog_index (HOST memory, no device work) checks the header line ("mgen
  * version=<4|5> ... type=binary_log\n" and its NUL, :1437-1518) and walks the records

@@ -9,6 +9,8 @@
 //   mgenx_log_recv_text (LogRecvEvent, :476: GMT or epoch timestamps, GPS, TTL, no data) ->
 //   mgenx_data_walk + mgenx_log_report_recv_text (the REPORT items LogRecvEvent logs) ->
 //   mgenx_text_interleave (per packet: analytic REPORT, RECV, received REPORTs) -> D2H.
+// A pcapng capture (what Wireshark writes) differs only in its front end: mgenx_pcapng_index
+// (host, the block walk) and mgenx_pcapng_parse; Run tells the two by the first four bytes.
 // A few small values come back to the host between stages (flow count, report count, text
 // sizes); everything per packet stays on the device.
 #pragma once
@@ -32,11 +34,14 @@ class Pcap2Mgen {
  public:
   Pcap2Mgen(Context& ctx, const PcapOptions& o) : ctx_(ctx), o_(o) {}
 
-  // The log text of a pcap file image (host memory).
+  // The log text of a pcap or pcapng file image (host memory); the first four bytes tell which
+  // (a Section Header Block's type reads 0A 0D 0D 0A in either byte order).
   std::string Run(const uint8_t* file, size_t nbytes) {
+    static const uint8_t kShb[4] = {0x0A, 0x0D, 0x0D, 0x0A};
+    if (nbytes >= 4 && memcmp(file, kShb, 4) == 0) return RunNg(file, nbytes);
     mgenx_pcap_info info;
     if (mgenx_pcap_index(file, nbytes, nullptr, 0, &info) != MGENX_OK)
-      throw Error("pcap2mgen: not a pcap file");
+      throw Error("pcap2mgen: not a pcap or pcapng file");
     std::vector<uint64_t> offs(info.n_records ? info.n_records : 1);
     (void)mgenx_pcap_index(file, nbytes, offs.data(), offs.size(), &info);
     const uint32_t n = (uint32_t)info.n_records;
@@ -74,6 +79,74 @@ class Pcap2Mgen {
                  "mgenx_pcap_snap");
       nbytes = buf_bytes;  // the records now reach into the scratch
     }
+    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
+  }
+
+  // The same over a resident pcapng image: d_pkt / d_pkt_if / d_ifaces as mgenx_pcapng_index
+  // gives them (flags: its info.flags).
+  std::string RunDeviceNg(uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_pkt,
+                          const uint32_t* d_pkt_if, uint32_t n, const mgenx_pcapng_if* d_ifaces,
+                          uint32_t n_ifaces, uint32_t link_type, uint32_t flags,
+                          uint64_t buf_bytes = 0) {
+    mgenx_ctx* c = ctx_.get();
+    hipStream_t s = ctx_.stream();
+    DeviceArray<uint64_t> udp_off(n), data_off(n);
+    DeviceArray<uint32_t> udp_len(n), rx_sec(n), rx_usec(n), cap_len(n);
+    DeviceArray<mgenx_addr> src(n);
+    DeviceArray<int32_t> ttl(n);
+    DeviceArray<uint8_t> status(n);
+    ctx_.Check(mgenx_pcapng_parse(c, d_buf, nbytes, d_pkt, d_pkt_if, n, d_ifaces, n_ifaces,
+                                  link_type, flags, udp_off.data(), udp_len.data(), src.data(),
+                                  ttl.data(), rx_sec.data(), rx_usec.data(), status.data(),
+                                  data_off.data(), cap_len.data(), s),
+               "mgenx_pcapng_parse");
+    if (buf_bytes > nbytes) {
+      ctx_.Check(mgenx_pcapng_snap(c, d_buf, nbytes, buf_bytes, data_off.data(), cap_len.data(),
+                                   n, status.data(), udp_off.data(), udp_len.data(), s),
+                 "mgenx_pcapng_snap");
+      nbytes = buf_bytes;
+    }
+    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
+  }
+
+ private:
+  // a pcapng capture: the block walk on the host, then as Run
+  std::string RunNg(const uint8_t* file, size_t nbytes) {
+    mgenx_pcapng_info info;
+    if (mgenx_pcapng_index(file, nbytes, nullptr, nullptr, 0, nullptr, 0, &info) != MGENX_OK)
+      throw Error("pcap2mgen: not a pcap or pcapng file");
+    std::vector<uint64_t> offs(info.n_records ? info.n_records : 1);
+    std::vector<uint32_t> pif(offs.size());
+    std::vector<mgenx_pcapng_if> ifs(info.n_ifaces ? info.n_ifaces : 1);
+    (void)mgenx_pcapng_index(file, nbytes, offs.data(), pif.data(), offs.size(), ifs.data(),
+                             (uint32_t)ifs.size(), &info);
+    const uint32_t n = (uint32_t)info.n_records;
+    if (n == 0) return std::string();
+    hipStream_t s = ctx_.stream();
+    DeviceArray<uint8_t> buf(nbytes + info.snap_bytes);
+    DeviceArray<uint64_t> pkt(n);
+    DeviceArray<uint32_t> pkt_if(n);
+    DeviceArray<mgenx_pcapng_if> d_ifs(info.n_ifaces);
+    check_hip(hipMemcpyAsync(buf.data(), file, nbytes, hipMemcpyHostToDevice, s), "H2D file");
+    check_hip(hipMemcpyAsync(pkt.data(), offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, s),
+              "H2D offsets");
+    check_hip(hipMemcpyAsync(pkt_if.data(), pif.data(), (size_t)n * 4, hipMemcpyHostToDevice, s),
+              "H2D interfaces");
+    check_hip(hipMemcpyAsync(d_ifs.data(), ifs.data(),
+                             (size_t)info.n_ifaces * sizeof(mgenx_pcapng_if),
+                             hipMemcpyHostToDevice, s),
+              "H2D interface table");
+    return RunDeviceNg(buf.data(), nbytes, pkt.data(), pkt_if.data(), n, d_ifs.data(),
+                       info.n_ifaces, info.link_type, info.flags, nbytes + info.snap_bytes);
+  }
+
+  // everything after the frame walk (either format): Unpack, analytics, the log lines
+  std::string Finish(uint8_t* d_buf, uint64_t nbytes, uint32_t n, DeviceArray<uint64_t>& udp_off,
+                     DeviceArray<uint32_t>& udp_len, DeviceArray<mgenx_addr>& src,
+                     DeviceArray<int32_t>& ttl, DeviceArray<uint32_t>& rx_sec,
+                     DeviceArray<uint32_t>& rx_usec) {
+    mgenx_ctx* c = ctx_.get();
+    hipStream_t s = ctx_.stream();
     Columns col(n);
     ctx_.Check(mgenx_unpack_batch(c, d_buf, nbytes, udp_off.data(), 0, udp_len.data(), 0, n,
                                   &col.cols, MGENX_OPT_SKIP_CRC, s),

@@ -26,6 +26,8 @@ from ._abi import (  # noqa: F401
     EVENT_NONE, EVENT_RECV, EVENT_RERR, EVENT_SEND, EVENT_REPORT, PARSE_OK, PARSE_MALFORMED,
     HAS_HOST, HAS_TTL, HAS_GPS, HAS_DATA, HAS_FLAGS, ERROR_RERR_NONE, ERROR_NOT_RECV,
     PARSE_NO_DAYS, LOGPARSE_COLS, LogparseOut,
+    PCAP_NG, PcapngInfo, PCAPNG_IF_DTYPE, PCAPNG_OK, PCAPNG_TRUNCATED, PCAPNG_BLOCK,
+    PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE, PCAPNG_TSRESOL, PCAPNG_CAPLEN,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_worker_create", "mgenx_worker_destroy", "mgenx_worker_unpack", "mgenx_worker_crc32",
     "mgenx_worker_pack", "mgenx_worker_stop", "mgenx_worker_info", "mgenx_worker_recv",
     "mgenx_worker_flow_update", "mgenx_text_index", "mgenx_log_parse_text",
+    "mgenx_pcapng_index", "mgenx_pcapng_parse", "mgenx_pcapng_snap",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -110,6 +113,10 @@ def load(diag: bool = False):
     L.mgenx_pcap_index.argtypes = [P, u64, P, u64, ctypes.POINTER(PcapInfo)]
     L.mgenx_pcap_parse.argtypes = [P, P, u64, P, u32, u32, u32, P, P, P, P, P, P, P, P]
     L.mgenx_pcap_snap.argtypes = [P, P, u64, u64, P, u32, u32, P, P, P, P]
+    L.mgenx_pcapng_index.argtypes = [P, u64, P, P, u64, P, u32, ctypes.POINTER(PcapngInfo)]
+    L.mgenx_pcapng_parse.argtypes = [P, P, u64, P, P, u32, P, u32, u32, u32, P, P, P, P, P, P, P,
+                                     P, P, P]
+    L.mgenx_pcapng_snap.argtypes = [P, P, u64, u64, P, P, u32, P, P, P, P]
     L.mgenx_binlog_index.argtypes = [P, u64, P, u64, ctypes.POINTER(BinlogInfo)]
     L.mgenx_convert_binary_log.argtypes = [P, P, u64, P, u32, u32, u32, P, u64, P, P]
     L.mgenx_text_index.argtypes = [P, P, u64, P, u64, P, P]
@@ -684,6 +691,39 @@ class Engine:
                                              _stream(self.device)), "mgenx_pcap_snap")
         return parsed
 
+    def pcapng_parse(self, buf, pkt_off, pkt_if, n, ifaces, n_ifaces, link_type, flags=0):
+        """mgenx_pcapng_parse over pcapng packet blocks (pkt_off, pkt_if and the interface
+        table as mgenx_pcapng_index gives them, on the device): pcap_parse's dict plus
+        data_off and cap_len (each packet's data, for pcapng_snap)."""
+        torch = self.torch
+        dev = buf.device
+        m = max(n, 1)
+        o = {"udp_off": torch.empty(m, dtype=torch.int64, device=dev),
+             "udp_len": torch.empty(m, dtype=torch.int32, device=dev),
+             "src": torch.empty(m * 20, dtype=torch.uint8, device=dev),
+             "ttl": torch.empty(m, dtype=torch.int32, device=dev),
+             "rx_sec": torch.empty(m, dtype=torch.int32, device=dev),
+             "rx_usec": torch.empty(m, dtype=torch.int32, device=dev),
+             "status": torch.empty(m, dtype=torch.uint8, device=dev),
+             "data_off": torch.empty(m, dtype=torch.int64, device=dev),
+             "cap_len": torch.empty(m, dtype=torch.int32, device=dev)}
+        self._check(self.lib.mgenx_pcapng_parse(
+            self.ctx, _ptr(buf), buf.numel(), _ptr(pkt_off), _ptr(pkt_if), n, _ptr(ifaces),
+            n_ifaces, link_type, flags, _ptr(o["udp_off"]), _ptr(o["udp_len"]), _ptr(o["src"]),
+            _ptr(o["ttl"]), _ptr(o["rx_sec"]), _ptr(o["rx_usec"]), _ptr(o["status"]),
+            _ptr(o["data_off"]), _ptr(o["cap_len"]), _stream(self.device)), "mgenx_pcapng_parse")
+        return o
+
+    def pcapng_snap(self, buf, file_bytes, n, parsed):
+        """mgenx_pcapng_snap: move the SNAPPED packets of `parsed` (pcapng_parse's dict) into
+        buf[file_bytes:], zero-extended, in place."""
+        self._check(self.lib.mgenx_pcapng_snap(self.ctx, _ptr(buf), file_bytes, buf.numel(),
+                                               _ptr(parsed["data_off"]), _ptr(parsed["cap_len"]),
+                                               n, _ptr(parsed["status"]), _ptr(parsed["udp_off"]),
+                                               _ptr(parsed["udp_len"]), _stream(self.device)),
+                    "mgenx_pcapng_snap")
+        return parsed
+
     def flow_export(self, flows, n_flows, out=None):
         if out is None:
             out = self.torch.empty(n_flows * 64, dtype=self.torch.uint8, device=flows.device)
@@ -848,6 +888,35 @@ def pcap_index(buf) -> tuple:
     if rc != 0:
         raise MgenxError("mgenx_pcap_index failed")
     return offs[:int(info.n_records)], info
+
+
+def pcapng_index(buf) -> tuple:
+    """mgenx_pcapng_index over a host pcapng image (bytes / numpy uint8): (packet block offsets
+    as uint64 numpy array, each packet's interface row as uint32 array, the interface table as
+    a PCAPNG_IF_DTYPE array, PcapngInfo).  Host work only (the block walk); info.status says
+    how the walk ended."""
+    L = load()
+    b = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+    info = PcapngInfo()
+    p = b.ctypes.data_as(ctypes.c_void_p)
+    if L.mgenx_pcapng_index(p, b.size, None, None, 0, None, 0, ctypes.byref(info)) != 0:
+        raise MgenxError("mgenx_pcapng_index: not a pcapng file")
+    offs = np.zeros(max(1, int(info.n_records)), np.uint64)
+    pkt_if = np.zeros(offs.size, np.uint32)
+    ifaces = np.zeros(max(1, int(info.n_ifaces)), PCAPNG_IF_DTYPE)
+    if L.mgenx_pcapng_index(p, b.size, offs.ctypes.data_as(ctypes.c_void_p),
+                            pkt_if.ctypes.data_as(ctypes.c_void_p), offs.size,
+                            ifaces.ctypes.data_as(ctypes.c_void_p), ifaces.size,
+                            ctypes.byref(info)) != 0:
+        raise MgenxError("mgenx_pcapng_index failed")
+    n = int(info.n_records)
+    return offs[:n], pkt_if[:n], ifaces[:int(info.n_ifaces)], info
+
+
+def is_pcapng(buf) -> bool:
+    """The first four bytes are a Section Header Block's type (it reads the same in either
+    byte order); a classic pcap file starts with one of its four magics instead."""
+    return bytes(memoryview(buf)[:4]) == b"\x0a\x0d\x0d\x0a"
 
 
 def binlog_index(buf) -> tuple:

@@ -162,6 +162,20 @@ LOG_EPOCH, LOG_NO_DATA, LOG_NO_GPS, LOG_SKIP_ERR = 0x1, 0x2, 0x4, 0x8
 FLOW_NONE = 0xFFFFFFFF
 DLT_EN10MB, DLT_LINUX_SLL = 1, 113
 PCAP_NSEC, PCAP_SWAPPED = 0x1, 0x2
+PCAP_NG = 0x4             # MGENX_PCAP_NG: offsets are pcapng packet blocks
+(PCAPNG_OK, PCAPNG_TRUNCATED, PCAPNG_BLOCK, PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE,
+ PCAPNG_TSRESOL, PCAPNG_CAPLEN) = range(8)
+PCAPNG_IF_DTYPE = np.dtype([("ts_units", "<u8"), ("ts_offset", "<i8"), ("snaplen", "<u4"),
+                            ("ts_binary", "u1"), ("rsv", "u1", (3,))])   # mgenx_pcapng_if
+assert PCAPNG_IF_DTYPE.itemsize == 24
+
+
+class PcapngInfo(ctypes.Structure):    # mgenx_pcapng_info
+    _fields_ = [("link_type", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("snaplen", ctypes.c_uint32), ("status", ctypes.c_int32),
+                ("n_records", ctypes.c_uint64), ("consumed", ctypes.c_uint64),
+                ("snap_bytes", ctypes.c_uint64), ("n_ifaces", ctypes.c_uint32),
+                ("n_sections", ctypes.c_uint32)]
 
 
 class BinlogInfo(ctypes.Structure):    # mgenx_binlog_info

@@ -77,11 +77,20 @@ extern "C" int mgenx_pcap_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes,
                                     mgenx_addr* dev_src, int32_t* dev_ttl, uint32_t* dev_rx_sec,
                                     uint32_t* dev_rx_usec, uint8_t* dev_status,
                                     hipStream_t stream);
+extern "C" int mgenx_pcapng_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes,
+                                      const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if,
+                                      uint32_t n, const mgenx_pcapng_if* dev_ifaces,
+                                      uint32_t n_ifaces, uint32_t link_type, uint32_t flags,
+                                      uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                                      mgenx_addr* dev_src, int32_t* dev_ttl,
+                                      uint32_t* dev_rx_sec, uint32_t* dev_rx_usec,
+                                      uint8_t* dev_status, uint64_t* dev_data_off,
+                                      uint32_t* dev_cap_len, hipStream_t stream);
 extern "C" int mgenx_pcap_snap_run(uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
-                                   const uint64_t* dev_pkt_off, uint32_t n, uint32_t flags,
-                                   uint8_t* dev_status, uint64_t* dev_udp_off,
-                                   uint32_t* dev_udp_len, uint64_t* need, void* scan_tmp,
-                                   size_t scan_bytes, hipStream_t stream);
+                                   const uint64_t* dev_pkt_off, const uint32_t* dev_cap_len,
+                                   uint32_t n, uint32_t flags, uint8_t* dev_status,
+                                   uint64_t* dev_udp_off, uint32_t* dev_udp_len, uint64_t* need,
+                                   void* scan_tmp, size_t scan_bytes, hipStream_t stream);
 extern "C" size_t mgenx_pcap_snap_scan_bytes(uint32_t n);
 extern "C" int mgenx_log_recv_run(void* ws, bool binary, const uint8_t* slab,
                                   uint64_t slab_bytes, const uint64_t* rec_off,
@@ -1480,9 +1489,12 @@ int mgenx_pcap_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
                               (hipStream_t)stream);
 }
 
-int mgenx_pcap_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
-                    const uint64_t* dev_pkt_off, uint32_t n, uint32_t flags, uint8_t* dev_status,
-                    uint64_t* dev_udp_off, uint32_t* dev_udp_len, void* stream) {
+// both snaps: dev_cap_len null = classic records at dev_pkt_off, else pcapng data offsets
+static int pcap_snap_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes,
+                         uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                         const uint32_t* dev_cap_len, uint32_t n, uint32_t flags,
+                         uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                         void* stream) {
   if (!ctx || buf_bytes < file_bytes || n > 0x7FFFFFFEu) return MGENX_EINVAL;
   if (n == 0) return MGENX_OK;
   if (!dev_buf || !dev_pkt_off || !dev_status || !dev_udp_off || !dev_udp_len) return MGENX_EINVAL;
@@ -1491,10 +1503,46 @@ int mgenx_pcap_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint6
   const size_t scan_b = mgenx_pcap_snap_scan_bytes(n);
   char* m = static_cast<char*>(ctx->snap.get(need_b + scan_b));
   if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_snap workspace");
-  const int rc = mgenx_pcap_snap_run(dev_buf, file_bytes, buf_bytes, dev_pkt_off, n, flags,
-                                     dev_status, dev_udp_off, dev_udp_len, (uint64_t*)m,
+  const int rc = mgenx_pcap_snap_run(dev_buf, file_bytes, buf_bytes, dev_pkt_off, dev_cap_len, n,
+                                     flags, dev_status, dev_udp_off, dev_udp_len, (uint64_t*)m,
                                      m + need_b, scan_b, (hipStream_t)stream);
   return rc == MGENX_OK ? MGENX_OK : set_err(ctx, hipGetLastError(), "pcap_snap");
+}
+
+int mgenx_pcap_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                    const uint64_t* dev_pkt_off, uint32_t n, uint32_t flags, uint8_t* dev_status,
+                    uint64_t* dev_udp_off, uint32_t* dev_udp_len, void* stream) {
+  return pcap_snap_any(ctx, dev_buf, file_bytes, buf_bytes, dev_pkt_off, nullptr, n, flags,
+                       dev_status, dev_udp_off, dev_udp_len, stream);
+}
+
+int mgenx_pcapng_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                       const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if, uint32_t n,
+                       const mgenx_pcapng_if* dev_ifaces, uint32_t n_ifaces, uint32_t link_type,
+                       uint32_t flags, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                       mgenx_addr* dev_src, int32_t* dev_ttl, uint32_t* dev_rx_sec,
+                       uint32_t* dev_rx_usec, uint8_t* dev_status, uint64_t* dev_data_off,
+                       uint32_t* dev_cap_len, void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_pkt_if || (n_ifaces && !dev_ifaces) || !dev_udp_off ||
+      !dev_udp_len || !dev_src || !dev_ttl || !dev_rx_sec || !dev_rx_usec || !dev_status ||
+      !dev_data_off || !dev_cap_len)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return mgenx_pcapng_parse_run(dev_buf, buf_bytes, dev_pkt_off, dev_pkt_if, n, dev_ifaces,
+                                n_ifaces, link_type, flags, dev_udp_off, dev_udp_len, dev_src,
+                                dev_ttl, dev_rx_sec, dev_rx_usec, dev_status, dev_data_off,
+                                dev_cap_len, (hipStream_t)stream);
+}
+
+int mgenx_pcapng_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                      const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      void* stream) {
+  if (n && !dev_cap_len) return MGENX_EINVAL;
+  return pcap_snap_any(ctx, dev_buf, file_bytes, buf_bytes, dev_data_off, dev_cap_len, n, 0,
+                       dev_status, dev_udp_off, dev_udp_len, stream);
 }
 
 // ---- ConvertBinaryLog (mgenMsg.cpp:1417-1900) ----

@@ -6,7 +6,8 @@ the analytic's REPORT line when a window closes), ``LogRecvEvent`` (the RECV lin
 timestamps, GPS, TTL, no data), and the REPORT lines of any reports the payload carries.
 Here the whole file goes to HBM once and every stage is one batch call of the C ABI:
 
-  mgenx_pcap_index (host: the record-header chain) -> mgenx_pcap_parse -> mgenx_unpack_batch
+  mgenx_pcap_index (host: the record-header chain) -> mgenx_pcap_parse [a pcapng capture:
+  mgenx_pcapng_index (host: the block walk) -> mgenx_pcapng_parse] -> mgenx_unpack_batch
   (MGENX_OPT_SKIP_CRC: Unpack alone) -> [mgenx_flow_lookup -> mgenx_flow_reduce_ex ->
   mgenx_flow_keys -> mgenx_report_build -> mgenx_log_report_text] -> mgenx_log_recv_text
   (MGENX_LOG_SKIP_ERR) -> mgenx_data_walk + mgenx_log_report_recv_text ->
@@ -20,8 +21,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import (DATA_CONTROLLER, FLOW_REPORT_DTYPE, LOG_EPOCH, LOG_NO_DATA, LOG_SKIP_ERR,
-               OPT_SKIP_CRC, TEXT_OWNER, TEXT_PER_RECORD, TEXT_SCATTER, Engine, MgenxError,
-               pcap_index)
+               OPT_SKIP_CRC, PCAP_NG, TEXT_OWNER, TEXT_PER_RECORD, TEXT_SCATTER, Engine, MgenxError,
+               is_pcapng, pcap_index, pcapng_index)
 
 
 def _quantized_window(window: float) -> float:
@@ -56,11 +57,19 @@ class Pcap2Mgen:
         self.opts = LOG_EPOCH if epoch else 0
 
     def upload(self, file):
-        """Host index walk + one H2D copy: (device file, device record offsets, PcapInfo)."""
+        """Host index walk + one H2D copy: (device file, device record offsets, PcapInfo).
+        A pcapng capture (told by its first four bytes): the offsets are its packet blocks,
+        the info is a PcapngInfo with two more attributes for run_device's `ng`, pkt_if and
+        ifaces (device tensors: each packet's interface row, the interface table)."""
         torch = self.eng.torch
         b = np.frombuffer(bytes(file), np.uint8) if not isinstance(file, np.ndarray) else file
-        offs, info = pcap_index(b)
         dev = f"cuda:{self.eng.device}"
+        if is_pcapng(b):
+            offs, pkt_if, ifaces, info = pcapng_index(b)
+            info.pkt_if = torch.from_numpy(pkt_if.view(np.int32).copy()).to(dev)
+            info.ifaces = torch.from_numpy(ifaces.view(np.uint8).copy()).to(dev)
+        else:
+            offs, info = pcap_index(b)
         # the file image, then scratch for packets cut by the snapshot length (mgenx_pcap_snap)
         buf = torch.zeros(b.size + int(info.snap_bytes), dtype=torch.uint8, device=dev)
         buf[:b.size] = torch.from_numpy(b.copy()).to(dev)
@@ -70,22 +79,33 @@ class Pcap2Mgen:
     def run(self, file) -> bytes:
         buf, pkt_off, info = self.upload(file)
         file_bytes = buf.numel() - int(info.snap_bytes)
+        ng = (info.pkt_if, info.ifaces) if info.flags & PCAP_NG else None
         text, _ = self.run_device(buf, pkt_off, int(info.n_records), info.link_type, info.flags,
-                                  file_bytes=file_bytes)
+                                  file_bytes=file_bytes, ng=ng)
         return text.cpu().numpy().tobytes()
 
-    def run_device(self, buf, pkt_off, n, link_type, flags, file_bytes=None):
+    def run_device(self, buf, pkt_off, n, link_type, flags, file_bytes=None, ng=None):
         """The device pipeline over a resident file: (text tensor, per-packet offsets).
         file_bytes: the file image's size when buf has scratch after it for snapped packets
-        (None: no scratch; packets cut by the snapshot length are skipped)."""
+        (None: no scratch; packets cut by the snapshot length are skipped).
+        ng: for a pcapng capture, (pkt_if, ifaces) on the device -- pkt_off then holds the
+        packet blocks' offsets (mgenx_pcapng_index)."""
         eng, torch = self.eng, self.eng.torch
         dev = buf.device
         if n == 0:
             return torch.empty(0, dtype=torch.uint8, device=dev), torch.zeros(
                 1, dtype=torch.int64, device=dev)
-        p = eng.pcap_parse(buf, pkt_off, n, link_type, flags)
-        if file_bytes is not None and file_bytes < buf.numel():
-            eng.pcap_snap(buf, file_bytes, pkt_off, n, flags, p)
+        snap = file_bytes is not None and file_bytes < buf.numel()
+        if ng is not None:
+            pkt_if, ifaces = ng
+            p = eng.pcapng_parse(buf, pkt_off, pkt_if, n, ifaces, ifaces.numel() // 24,
+                                 link_type, flags)
+            if snap:
+                eng.pcapng_snap(buf, file_bytes, n, p)
+        else:
+            p = eng.pcap_parse(buf, pkt_off, n, link_type, flags)
+            if snap:
+                eng.pcap_snap(buf, file_bytes, pkt_off, n, flags, p)
         cols = eng.unpack(buf, n, rec_off=p["udp_off"], rec_len=p["udp_len"], opts=OPT_SKIP_CRC,
                           ext=True)
         sources = []
@@ -170,7 +190,7 @@ class Pcap2Mgen:
 
 
 def pcap2mgen(file, analytics=False, log_rx=True, window=1.0, epoch=False, device=0) -> bytes:
-    """One-shot helper: the log text of a pcap file image."""
+    """One-shot helper: the log text of a pcap or pcapng file image."""
     eng = Engine(device)
     try:
         return Pcap2Mgen(eng, analytics, log_rx, window, epoch).run(file)

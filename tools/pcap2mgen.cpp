@@ -4,6 +4,7 @@
 // (:25-248): report, analytic, infile <f>, outfile <f>, trace, rxlog on|off, flush,
 // window <sec> -- given bare, as there (the table's +/- only says whether an argument
 // follows), each matched case-insensitively by a unique prefix; stdin / stdout by default.
+// The input is a pcap or a pcapng capture (told apart by its first bytes, no option needed).
 // The whole capture is read, decoded on the device by mgenx::Pcap2Mgen
 // (include/mgenx_pcap.hpp) and the log written in one piece.  "trace" (MAC addresses in
 // front of each line) is not supported and is reported as such; "flush" has nothing to do
