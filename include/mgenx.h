@@ -10,9 +10,9 @@
  * launches (the stream scans, mgenx_pack_tcp) read small results back, and calls with
  * scratch grow it (hipMalloc) the first time a larger batch arrives -- warm them up with
  * the largest batch before capturing a graph.  The log / report / walk formatters keep
- * one workspace per stream; the stream scans, mgenx_flow_reduce, mgenx_pack_tcp and
- * mgenx_tcp_rx_persist keep one per context, so those run on one stream at a time per
- * context (one context per concurrent stream).
+ * one workspace per stream; the stream scans, mgenx_flow_reduce, mgenx_flow_dist,
+ * mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per context, so those run on one stream
+ * at a time per context (one context per concurrent stream).
  *
  * Return value: 0 = launched, <0 = argument/launch error (MGENX_E*).  Per-record
  * outcomes go to the `err` column with MgenMsg::Error codes (include/mgenMsg.h:63-70).
@@ -32,6 +32,8 @@
  *   mgenx_crc32_update  <- MgenMsg::ComputeCRC32      include/mgenMsg.h:201-203
  *   mgenx_allreduce_flows  the per-flow counter merge of flow-sharded analytics (RCCL)
  *   mgenx_flow_lookup   <- MgenAnalyticTable::FindFlow  include/mgenAnalytic.h:387
+ *   mgenx_flow_dist     no reference code: the latency distribution, jitter and re-ordering
+ *                       the manual reads logs for (doc/mgen.xml:3399-3450)
  */
 #ifndef MGENX_H
 #define MGENX_H
@@ -589,6 +591,71 @@ int mgenx_flow_reduce_rows(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const m
                            uint32_t* dev_report_count, uint32_t* dev_report_rec, void* stream);
 int mgenx_flow_export(mgenx_ctx* ctx, const mgenx_flow_state* dev_flows, uint32_t n_flows,
                       mgenx_flow_counters* dev_out, void* stream);
+
+/* ---- per-flow delivery statistics: latency histogram, jitter, reordering ----
+ * What the MGEN manual names as the uses of a log beside rate and loss (doc/mgen.xml, the
+ * table at 3399-3450): the distribution of the delivery latency, how far it moves from one
+ * message to the next, and how many messages arrive out of order.  Integer arithmetic on
+ * microseconds over the columns mgenx_flow_reduce takes; the result does not depend on the
+ * order in which workgroups finish and equals a serial walk of the records exactly.
+ *
+ * Records i < n with dev_flow_idx[i] < n_flows count, in receive order (others are skipped,
+ * MGENX_FLOW_NONE included).  For record k of a flow, in signed 64-bit (the u32 columns
+ * widened first; a tx_usec >= 10^6 is taken as it is):
+ *   rx  = rx_sec * 10^6 + rx_usec
+ *   lat = (rx_sec - tx_sec) * 10^6 + rx_usec - tx_usec
+ * Per flow (struct mgenx_flow_dist, 160 B; the name is also the function's, so C code writes
+ * the struct keyword):
+ *   n, bytes             records; sum of msg_len
+ *   lat_sum/min/max      over all records (INT64_MAX / INT64_MIN while n == 0; the sum wraps)
+ *   lat_neg, lat_over    records with lat < 0, with lat >= 2^32
+ *   jitter_sum/max       abs(lat_k - lat_{k-1}) over consecutive records of the flow (n - 1
+ *                        terms; jitter_sum / (n - 1) is the mean jitter, not RFC 3550's filter)
+ *   gap_min/max          rx_k - rx_{k-1}, signed (INT64_MAX / INT64_MIN below two records)
+ *   reordered, reorder_sum, reorder_max
+ *                        record k is reordered iff seq_k < M, M the largest seq among the
+ *                        flow's earlier records (plain unsigned compare: a sequence wrap is not
+ *                        followed; a record equal to M is not reordered; duplicates are not
+ *                        removed); its distance is M - seq_k
+ *   seq_min, seq_max     over all records (UINT32_MAX / 0 while n == 0)
+ *   first_rx, last_rx, last_lat   carried between calls (0 while n == 0)
+ * Histogram (optional): dev_hist[f * MGENX_FLOW_DIST_BINS + b] counts the records of flow f
+ * with 0 <= lat < 2^32 in bin b = mgenx_flow_dist_bin(lat): one bin per value below 64 us,
+ * then 32 bins per octave (bin b >= 64 starts at mgenx_flow_dist_bin_lo(b); bin_lo(896) =
+ * 2^32; mgenx_flow_dist_bin of a value >= 2^32 gives 896, no bin).
+ * Streaming: state and histogram persist in the caller's arrays; calls over consecutive
+ * batches leave the bytes one call over the concatenation leaves.
+ * mgenx_flow_dist_quantiles: dev_out[f * n_q + j] for permille[j] in 1..1000 (host array;
+ * anything else is MGENX_EINVAL): with rank r = max(1, (q * n + 999) / 1000) over the order
+ * lat_neg records < bins 0..895 < lat_over records, -1 when the rank falls among the negative
+ * latencies, the inclusive upper edge of its bin, 2^32 among the overflows, INT64_MIN for a
+ * flow without records.  The r-th smallest latency x has bin_lo <= x <= value.
+ * Synchronous on `stream` only when the workspace must grow. */
+#define MGENX_FLOW_DIST_BINS 896
+struct mgenx_flow_dist {            /* 160 B; set up by mgenx_flow_dist_init */
+  uint64_t n, bytes;
+  int64_t  lat_sum, lat_min, lat_max;
+  uint64_t lat_neg, lat_over;
+  uint64_t jitter_sum, jitter_max;
+  int64_t  gap_min, gap_max;
+  uint64_t reordered, reorder_sum;
+  uint32_t reorder_max, seq_min, seq_max, rsv32;
+  int64_t  first_rx, last_rx, last_lat;
+  uint64_t rsv[2];
+};
+int mgenx_flow_dist_init(mgenx_ctx* ctx, struct mgenx_flow_dist* dev_dist, uint64_t* dev_hist,
+                         uint32_t n_flows, void* stream);
+int mgenx_flow_dist(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_seq,
+                    const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                    const uint16_t* dev_msg_len, const uint32_t* dev_rx_sec,
+                    const uint32_t* dev_rx_usec, uint32_t n, struct mgenx_flow_dist* dev_dist,
+                    uint64_t* dev_hist, uint32_t n_flows, void* stream);
+int mgenx_flow_dist_quantiles(mgenx_ctx* ctx, const struct mgenx_flow_dist* dev_dist,
+                              const uint64_t* dev_hist, uint32_t n_flows,
+                              const uint32_t* permille, uint32_t n_q, int64_t* dev_out,
+                              void* stream);
+uint32_t mgenx_flow_dist_bin(uint64_t v);
+uint64_t mgenx_flow_dist_bin_lo(uint32_t bin);
 
 
 /* ---- MgenAnalyticTable::FindFlow for batches (mgenAnalytic.cpp:312-328) ----

@@ -11,6 +11,8 @@
 //                  + WriteChecksum in the UDP/SINK send order (mgenTransport.cpp:1011-1031);
 //   FlowAnalytics  Mgen::UpdateRecvAnalytics (mgen.cpp:1027-1070): FindFlow by
 //                  (src, dst, flow id) -> MgenAnalytic::Update per record, reports out;
+//   FlowDistribution  the delivery statistics a log is read for (latency histogram and
+//                  quantiles, jitter, receive gaps, reordering): mgenx_flow_dist per batch;
 //   ShardedScan    MgenTcpTransport / MgenAppSinkTransport framing (mgenTransport.cpp:
 //                  1683-1760, mgenAppSinkTransport.cpp:369-434) of ONE stream split over the
 //                  ranks of a job (the stitch protocol of include/mgenx.h, "sharded framing",
@@ -593,6 +595,67 @@ class FlowAnalytics {
   DeviceArray<uint32_t> count_;
   DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
   std::map<std::tuple<std::string, std::string, uint32_t>, uint32_t> index_;
+};
+
+// ---- delivery statistics: latency histogram, jitter, receive gaps, reordering ------------
+// mgenx_flow_dist over batches (include/mgenx.h): integer microseconds, state and histogram
+// kept on the device across Update calls.  Flow indices as FlowAnalytics::FindFlow gives them.
+class FlowDistribution {
+ public:
+  typedef struct mgenx_flow_dist State;
+  FlowDistribution(Context& ctx, uint32_t maxFlows)
+      : ctx_(ctx), max_(maxFlows), dist_(maxFlows),
+        hist_((size_t)maxFlows * MGENX_FLOW_DIST_BINS) {
+    ctx_.Check(mgenx_flow_dist_init(ctx_.get(), dist_.data(), hist_.data(), maxFlows,
+                                    ctx_.stream()), "mgenx_flow_dist_init");
+  }
+  // Every record of a decoded batch, in receive order (FlowAnalytics::Update's arguments).
+  void Update(const RecvBatch& b, const std::vector<uint32_t>& flowIdx,
+              const std::vector<uint32_t>& rxSec, const std::vector<uint32_t>& rxUsec) {
+    const uint32_t n = b.Size();
+    d_idx_.Resize(n);
+    d_rxs_.Resize(n);
+    d_rxu_.Resize(n);
+    hipStream_t s = ctx_.stream();
+    check_hip(hipMemcpyAsync(d_idx_.data(), flowIdx.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxs_.data(), rxSec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxu_.data(), rxUsec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    ctx_.Check(mgenx_flow_dist(ctx_.get(), d_idx_.data(), b.DevSeq(), b.DevTxSec(), b.DevTxUsec(),
+                               b.DevMsgLen(), d_rxs_.data(), d_rxu_.data(), n, dist_.data(),
+                               hist_.data(), max_, s), "mgenx_flow_dist");
+    ctx_.Sync();  // the host vectors are the caller's again
+  }
+  // the per-flow state so far
+  std::vector<State> Dist() { return Download(dist_, max_); }
+  // counts per flow and bin: [flow * MGENX_FLOW_DIST_BINS + bin]
+  std::vector<uint64_t> Histogram() { return Download(hist_, (size_t)max_ * MGENX_FLOW_DIST_BINS); }
+  // out[flow * permille.size() + j]: the latency at permille[j] (1..1000), a bin's upper edge
+  std::vector<int64_t> Quantiles(const std::vector<uint32_t>& permille) {
+    d_q_.Resize(std::max<size_t>((size_t)max_ * permille.size(), 1));
+    ctx_.Check(mgenx_flow_dist_quantiles(ctx_.get(), dist_.data(), hist_.data(), max_,
+                                         permille.data(), (uint32_t)permille.size(), d_q_.data(),
+                                         ctx_.stream()), "mgenx_flow_dist_quantiles");
+    return Download(d_q_, (size_t)max_ * permille.size());
+  }
+  State* DevDist() const { return dist_.data(); }
+  uint64_t* DevHistogram() const { return hist_.data(); }
+
+ private:
+  template <typename T>
+  std::vector<T> Download(const DeviceArray<T>& d, size_t n) {
+    std::vector<T> out(n);
+    if (n)
+      check_hip(hipMemcpyAsync(out.data(), d.data(), n * sizeof(T), hipMemcpyDeviceToHost,
+                               ctx_.stream()), "D2H");
+    ctx_.Sync();
+    return out;
+  }
+  Context& ctx_;
+  uint32_t max_;
+  DeviceArray<State> dist_;
+  DeviceArray<uint64_t> hist_;
+  DeviceArray<int64_t> d_q_;
+  DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
 };
 
 // ---- sharded stream framing: one TCP / SINK stream over the ranks of a job --------------

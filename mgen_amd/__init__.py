@@ -28,6 +28,7 @@ from ._abi import (  # noqa: F401
     PARSE_NO_DAYS, LOGPARSE_COLS, LogparseOut,
     PCAP_NG, PcapngInfo, PCAPNG_IF_DTYPE, PCAPNG_OK, PCAPNG_TRUNCATED, PCAPNG_BLOCK,
     PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE, PCAPNG_TSRESOL, PCAPNG_CAPLEN,
+    FLOW_DIST_BINS, FLOW_DIST_DTYPE,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "mgenx_worker_pack", "mgenx_worker_stop", "mgenx_worker_info", "mgenx_worker_recv",
     "mgenx_worker_flow_update", "mgenx_text_index", "mgenx_log_parse_text",
     "mgenx_pcapng_index", "mgenx_pcapng_parse", "mgenx_pcapng_snap",
+    "mgenx_flow_dist_init", "mgenx_flow_dist", "mgenx_flow_dist_quantiles",
+    "mgenx_flow_dist_bin", "mgenx_flow_dist_bin_lo",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -146,6 +149,13 @@ def load(diag: bool = False):
     L.mgenx_flow_reduce.argtypes = [P, P, P, P, P, P, P, P, u32, P, u32, P, u32, P, P]
     L.mgenx_flow_reduce_rows.argtypes = [P, P, P, P, P, u32, P, u32, P, u32, P, P, P]
     L.mgenx_flow_export.argtypes = [P, P, u32, P, P]
+    L.mgenx_flow_dist_init.argtypes = [P, P, P, u32, P]
+    L.mgenx_flow_dist.argtypes = [P, P, P, P, P, P, P, P, u32, P, P, u32, P]
+    L.mgenx_flow_dist_quantiles.argtypes = [P, P, P, u32, ctypes.POINTER(u32), u32, P, P]
+    L.mgenx_flow_dist_bin.argtypes = [u64]
+    L.mgenx_flow_dist_bin.restype = u32
+    L.mgenx_flow_dist_bin_lo.argtypes = [u32]
+    L.mgenx_flow_dist_bin_lo.restype = u64
     L.mgenx_log_recv_text.argtypes = [P, P, P, u64, ctypes.POINTER(MgenxCols), P, P, P, P, u32,
                                       i32, u32, P, u64, P, P]
     L.mgenx_log_recv_binary.argtypes = [P, P, u64, P, u64, P, ctypes.POINTER(MgenxCols), P, P,
@@ -587,6 +597,44 @@ class Engine:
         self._check(rc, "mgenx_flow_reduce_rows")
         return report_count
 
+    def flow_dist_init(self, n_flows, hist=True):
+        """Fresh per-flow delivery statistics (mgenx_flow_dist_init): (dist, hist), a uint8
+        tensor of n_flows x 160 B (FLOW_DIST_DTYPE) and an int64 tensor of n_flows x
+        FLOW_DIST_BINS counts (None with hist=False)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        dist = torch.empty(n_flows * FLOW_DIST_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        h = torch.empty((n_flows, FLOW_DIST_BINS), dtype=torch.int64, device=dev) if hist else None
+        self._check(self.lib.mgenx_flow_dist_init(self.ctx, _ptr(dist), _ptr(h), n_flows,
+                                                  _stream(self.device)), "mgenx_flow_dist_init")
+        return dist, h
+
+    def flow_dist(self, dist, hist, n_flows, flow_idx, seq, tx_sec, tx_usec, msg_len, rx_sec,
+                  rx_usec, n=None):
+        """Latency / jitter / gap / reordering statistics over records in receive order
+        (mgenx_flow_dist), added to dist and (unless None) hist; batches may follow each
+        other."""
+        n = flow_idx.numel() if n is None else n
+        self._check(self.lib.mgenx_flow_dist(self.ctx, _ptr(flow_idx), _ptr(seq), _ptr(tx_sec),
+                                             _ptr(tx_usec), _ptr(msg_len), _ptr(rx_sec),
+                                             _ptr(rx_usec), n, _ptr(dist), _ptr(hist), n_flows,
+                                             _stream(self.device)), "mgenx_flow_dist")
+
+    def flow_dist_quantiles(self, dist, hist, n_flows, permille, out=None):
+        """Latency quantiles from the histogram (mgenx_flow_dist_quantiles): an int64 tensor
+        [n_flows, len(permille)] of bin upper edges in microseconds (-1 among the negative
+        latencies, 2**32 among those past the histogram, INT64_MIN for an empty flow)."""
+        torch = self.torch
+        q = (ctypes.c_uint32 * len(permille))(*[int(v) for v in permille])
+        if out is None:
+            out = torch.empty((n_flows, len(permille)), dtype=torch.int64,
+                              device=f"cuda:{self.device}")
+        self._check(self.lib.mgenx_flow_dist_quantiles(self.ctx, _ptr(dist), _ptr(hist), n_flows,
+                                                       q, len(permille), _ptr(out),
+                                                       _stream(self.device)),
+                    "mgenx_flow_dist_quantiles")
+        return out
+
     def flow_keys(self, table, n_flows, protocol=1, keys=None):
         """The report_msg key of every flow index < n_flows (mgenx_flow_keys): a uint8
         tensor of n_flows x 48 (mgenx_report_key)."""
@@ -987,6 +1035,57 @@ def analyze_text_log(log_bytes, window=1.0, day_base=0, device=0) -> tuple:
         torch.cuda.synchronize(device)
         return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
                 counters.cpu().numpy().view(FLOW_COUNTERS_DTYPE)[:nf].copy(), n, n_bad)
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
+        eng.close()
+
+
+def flow_dist_bin(v: int) -> int:
+    """The histogram bin of a latency 0 <= v < 2**32 us (mgenx_flow_dist_bin; 896 past that)."""
+    return int(load().mgenx_flow_dist_bin(int(v)))
+
+
+def flow_dist_bin_lo(b: int) -> int:
+    """The lowest latency of bin b (mgenx_flow_dist_bin_lo; bin_lo(896) = 2**32)."""
+    return int(load().mgenx_flow_dist_bin_lo(int(b)))
+
+
+def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
+                          device=0) -> tuple:
+    """Per-flow delivery statistics of an MGEN text log, on the GPU: line index -> parse ->
+    FindFlow -> mgenx_flow_dist -> quantiles.  Returns (keys, dist, quantiles, hist, n_lines,
+    n_malformed): numpy arrays of REPORT_KEY_DTYPE and FLOW_DIST_DTYPE, int64 [n_flows,
+    len(permille)] and uint64 [n_flows, FLOW_DIST_BINS], flows in analyze_text_log's order."""
+    import torch
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
+        line_off, n = eng.text_index(text)
+        empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_DIST_DTYPE),
+                 np.zeros((0, len(permille)), np.int64), np.zeros((0, FLOW_DIST_BINS), np.uint64))
+        if n == 0:
+            return empty + (0, 0)
+        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+        n_bad = int((p["status"] != PARSE_OK).sum().item())
+        table = eng.flow_table(max(n, 16))
+        flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
+        nf = int(n_flows.item())
+        if nf == 0:
+            return empty + (n, n_bad)
+        dist, hist = eng.flow_dist_init(nf)
+        eng.flow_dist(dist, hist, nf, flow_idx, p["seq_num"], p["tx_sec"], p["tx_usec"],
+                      p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+        quant = eng.flow_dist_quantiles(dist, hist, nf, permille)
+        recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
+        proto = int(p["protocol"][recv][0].item())
+        keys = eng.flow_keys(table, nf, protocol=proto)
+        torch.cuda.synchronize(device)
+        return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
+                dist.cpu().numpy().view(FLOW_DIST_DTYPE)[:nf].copy(), quant.cpu().numpy(),
+                hist.cpu().numpy().view(np.uint64), n, n_bad)
     finally:
         if table is not None:
             eng.flow_table_destroy(table)

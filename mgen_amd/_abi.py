@@ -140,6 +140,15 @@ FLOW_STATE_DTYPE = np.dtype([
     ("n_reports", "<u8"), ("rsv", "<u8", (2,))])
 assert FLOW_STATE_DTYPE.itemsize == FLOW_STATE_BYTES
 assert FLOW_REPORT_DTYPE.itemsize == 96 and FLOW_COUNTERS_DTYPE.itemsize == 64
+# struct mgenx_flow_dist (160 B) and the latency histogram's bins per flow
+FLOW_DIST_BINS = 896
+FLOW_DIST_DTYPE = np.dtype([
+    ("n", "<u8"), ("bytes", "<u8"), ("lat_sum", "<i8"), ("lat_min", "<i8"), ("lat_max", "<i8"),
+    ("lat_neg", "<u8"), ("lat_over", "<u8"), ("jitter_sum", "<u8"), ("jitter_max", "<u8"),
+    ("gap_min", "<i8"), ("gap_max", "<i8"), ("reordered", "<u8"), ("reorder_sum", "<u8"),
+    ("reorder_max", "<u4"), ("seq_min", "<u4"), ("seq_max", "<u4"), ("rsv32", "<u4"),
+    ("first_rx", "<i8"), ("last_rx", "<i8"), ("last_lat", "<i8"), ("rsv", "<u8", (2,))])
+assert FLOW_DIST_DTYPE.itemsize == 160
 
 
 # ---- pcap2mgen / text interleave (include/mgenx.h) ----

@@ -1549,3 +1549,64 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
   }
   return MGENX_OK;
 }
+
+// The radix ordering alone, for mgenx_flow_dist (mgenx_flowdist.hip): flow_keys_kernel, the
+// stable pair sort and flow_bounds_kernel as the radix path above runs them.  `mem` holds
+// mgenx_flow_sort_ws(n, n_flows) bytes.  keys[p] = the flow of sorted position p (n_flows for a
+// skipped record), order[p] = its record, bnd[f] = the first position with flow >= f
+// (f = 0..n_flows).
+static uint32_t flow_key_bits(uint32_t n_flows) {
+  uint32_t key_bits = 1;
+  while (key_bits < 32 && (1ull << key_bits) <= n_flows) key_bits++;
+  return key_bits;
+}
+
+static size_t flow_sort_cub_bytes(uint32_t n, uint32_t n_flows) {
+  size_t cub_bytes = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const uint32_t*)nullptr,
+                                           (uint32_t*)nullptr, (const uint32_t*)nullptr,
+                                           (uint32_t*)nullptr, (int)n, 0,
+                                           (int)flow_key_bits(n_flows), (hipStream_t)0);
+  return cub_bytes;
+}
+
+extern "C" size_t mgenx_flow_sort_ws(uint32_t n, uint32_t n_flows) {
+  return 4 * a256((size_t)n * 4) + a256(((size_t)n_flows + 1) * 4) +
+         a256(flow_sort_cub_bytes(n, n_flows));
+}
+
+extern "C" int mgenx_flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n,
+                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
+                                   const uint32_t** bnd, hipStream_t stream, char* err,
+                                   size_t errn) {
+  const size_t nb = a256((size_t)n * 4), bb = a256(((size_t)n_flows + 1) * 4);
+  size_t cub_bytes = flow_sort_cub_bytes(n, n_flows);
+  char* p = static_cast<char*>(mem);
+  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  uint32_t* keys_in = (uint32_t*)take(nb);
+  uint32_t* keys_out = (uint32_t*)take(nb);
+  uint32_t* vals_in = (uint32_t*)take(nb);
+  uint32_t* vals_out = (uint32_t*)take(nb);
+  uint32_t* d_bnd = (uint32_t*)take(bb);
+  void* cub_tmp = take(a256(cub_bytes));
+  hipLaunchKernelGGL(flow_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, flow_idx, n,
+                     n_flows, keys_in, vals_in);
+  hipError_t e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_in, keys_out, vals_in,
+                                                    vals_out, (int)n, 0,
+                                                    (int)flow_key_bits(n_flows), stream);
+  if (e != hipSuccess) {
+    snprintf(err, errn, "flow_dist sort: %s", hipGetErrorString(e));
+    return MGENX_EDEVICE;
+  }
+  hipLaunchKernelGGL(flow_bounds_kernel, dim3((n_flows + 1u + 255u) / 256u), dim3(256), 0, stream,
+                     keys_out, n, n_flows, d_bnd);
+  e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(err, errn, "flow_dist sort: %s", hipGetErrorString(e));
+    return MGENX_EDEVICE;
+  }
+  *keys = keys_out;
+  *order = vals_out;
+  *bnd = d_bnd;
+  return MGENX_OK;
+}

@@ -22,6 +22,7 @@
 
 
 #include "mgenx_kernels.hpp"
+#include "mgenx_flowdist.hpp"
 #if MGENX_DIAG
 #include "mgenx_diag.h"
 #endif
@@ -115,6 +116,19 @@ extern "C" int mgenx_flow_reduce_run(void* ws, const uint32_t* flow_idx, const u
                                      mgenx_flow_report* reports, uint32_t per_flow,
                                      uint32_t* report_count, uint32_t* report_rec,
                                      hipStream_t stream, char* err, size_t errn);
+extern "C" void* mgenx_flowdist_ws_new();
+extern "C" void mgenx_flowdist_ws_free(void* p);
+extern "C" int mgenx_flow_dist_init_run(struct mgenx_flow_dist* dist, uint64_t* hist,
+                                        uint32_t n_flows, hipStream_t stream);
+extern "C" int mgenx_flow_dist_run(void* ws, const uint32_t* flow_idx, const uint32_t* seq,
+                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                                   struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
+                                   hipStream_t stream, char* err, size_t errn);
+extern "C" int mgenx_flow_dist_quantiles_run(const struct mgenx_flow_dist* dist,
+                                             const uint64_t* hist, uint32_t n_flows,
+                                             const uint32_t* permille, uint32_t n_q, int64_t* out,
+                                             hipStream_t stream);
 
 extern "C" int mgenx_binlog_parse_exec(const uint8_t* buf, const uint64_t* rec_off, uint32_t n,
                                        uint64_t* msg_off, uint32_t* msg_len, mgenx_addr* src,
@@ -175,6 +189,7 @@ struct mgenx_ctx {
   double* d_rq = nullptr;         // report quantizer tables (mgenx::kRq*), built with host libm
   void* scan_ws = nullptr;        // stream-scan workspace (mgenx_scan.hip), grown on demand
   void* flow_ws = nullptr;        // flow-reduce workspace (mgenx_analytic.hip), grown on demand
+  void* flowdist_ws = nullptr;    // flow-dist workspace (mgenx_flowdist.hip), grown on demand
   void* log_ws = nullptr;         // log-format workspace (mgenx_log.hip), grown on demand
   void* tcp_ws = nullptr;         // TCP transmit workspace (mgenx_pack_tcp), grown on demand
   size_t tcp_ws_bytes = 0;
@@ -377,6 +392,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
                 c->d_sink, c->d_rq};
   if (c->scan_ws) mgenx_scan_ws_free(c->scan_ws);
   if (c->flow_ws) mgenx_flow_ws_free(c->flow_ws);
+  if (c->flowdist_ws) mgenx_flowdist_ws_free(c->flowdist_ws);
   if (c->log_ws) mgenx_log_ws_free(c->log_ws);
   mgenx::dev_free(c->tcp_ws);
   mgenx::dev_free(c->tcp_plan);
@@ -890,6 +906,48 @@ int mgenx_flow_reduce_rows(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const m
                                dev_reports, per_flow, dev_report_count, dev_report_rec,
                                (hipStream_t)stream, ctx->err, sizeof(ctx->err));
 }
+
+int mgenx_flow_dist_init(mgenx_ctx* ctx, struct mgenx_flow_dist* dev_dist, uint64_t* dev_hist,
+                         uint32_t n_flows, void* stream) {
+  if (!ctx || (n_flows && !dev_dist) || n_flows > 0x7FFFFFFFu) return MGENX_EINVAL;
+  if (n_flows == 0) return MGENX_OK;
+  hipSetDevice(ctx->device);
+  return mgenx_flow_dist_init_run(dev_dist, dev_hist, n_flows, (hipStream_t)stream);
+}
+
+int mgenx_flow_dist(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_seq,
+                    const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                    const uint16_t* dev_msg_len, const uint32_t* dev_rx_sec,
+                    const uint32_t* dev_rx_usec, uint32_t n, struct mgenx_flow_dist* dev_dist,
+                    uint64_t* dev_hist, uint32_t n_flows, void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n == 0 || n_flows == 0) return MGENX_OK;
+  if (!dev_flow_idx || !dev_seq || !dev_tx_sec || !dev_tx_usec || !dev_msg_len || !dev_rx_sec ||
+      !dev_rx_usec || !dev_dist || n > 0x7FFFFFFFu || n_flows > 0x7FFFFFFFu)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (!ctx->flowdist_ws) ctx->flowdist_ws = mgenx_flowdist_ws_new();
+  return mgenx_flow_dist_run(ctx->flowdist_ws, dev_flow_idx, dev_seq, dev_tx_sec, dev_tx_usec,
+                             dev_msg_len, dev_rx_sec, dev_rx_usec, n, dev_dist, dev_hist, n_flows,
+                             (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_flow_dist_quantiles(mgenx_ctx* ctx, const struct mgenx_flow_dist* dev_dist,
+                              const uint64_t* dev_hist, uint32_t n_flows,
+                              const uint32_t* permille, uint32_t n_q, int64_t* dev_out,
+                              void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n_flows == 0 || n_q == 0) return MGENX_OK;
+  if (!dev_dist || !dev_hist || !permille || !dev_out) return MGENX_EINVAL;
+  for (uint32_t j = 0; j < n_q; j++)
+    if (permille[j] < 1u || permille[j] > 1000u) return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return mgenx_flow_dist_quantiles_run(dev_dist, dev_hist, n_flows, permille, n_q, dev_out,
+                                       (hipStream_t)stream);
+}
+
+uint32_t mgenx_flow_dist_bin(uint64_t v) { return mgenx::flow_dist_bin(v); }
+uint64_t mgenx_flow_dist_bin_lo(uint32_t bin) { return mgenx::flow_dist_bin_lo(bin); }
 
 static int log_recv(mgenx_ctx* ctx, bool binary, const uint8_t* dev_slab, uint64_t slab_bytes,
                     const uint64_t* dev_rec_off, const uint32_t* dev_rec_len, uint64_t stride,
