@@ -1463,19 +1463,23 @@ unpack_fixed_kernel(UnpackParams p, uint32_t expect) {
 // headline layout -- reading and writing in separate phases.  On the MI355X boxes where
 // mixing the 32-B row stores into the 1 GiB read stream costs most (config 2): the read
 // pattern alone takes 168 us, with the row stores interleaved 201 us.  So each wave keeps
-// the rows of its last K = 16 groups in registers (a shift register, 2 dwords per group and
-// lane) and stores them in one burst every K groups and at its end: for config 2 (16 groups
-// per wave) one burst, after the wave's reads (measured 0.194 ms against 0.215 ms for the
-// interleaved kernel on the same box; K = 12 with two bursts: 0.204 ms).  The registers come
-// from a shorter load ring: RS = 4 rows in flight per wave (row r + 4 of the wave's row stream
-// is loaded as row r is consumed; 4 KiB per wave, 64 KiB per CU).
+// the rows of its last K = 16 groups in registers (2 dwords per group and lane, written by a
+// wave-uniform indexed move) and stores them in one burst every K groups and at its end: for
+// config 2 (16 groups per wave) one burst, after the wave's reads (measured 0.194 ms against
+// 0.215 ms for the interleaved kernel on the same box; K = 12 with two bursts: 0.204 ms).  The
+// registers come from a shorter load ring: RS = 4 rows per wave (4 KiB per wave, 64 KiB per
+// CU), reloaded as a BLOCK: when the last of the RS rows is consumed, rows r + 4 .. r + 7 of
+// the wave's row stream are requested by four back-to-back loads.  Rows 2j and 2j + 1 are the
+// halves of a record's 128-byte line, and a block is two whole lines per record; requesting
+// them together measured 4% faster than one reload per consumed row (0.187 against 0.195 ms,
+// DESIGN 4.1), although the wave then computes with nothing of its own in flight.
 // Semantics are those of unpack_fixed_kernel<NR, 0, true, true>.
 template <int NR, int RS = 4, int K = 16>
 __global__ void __launch_bounds__(kUnpackThreads)
 unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
   static_assert(NR == 8 || NR == 16, "ring kernel: 512- or 1024-byte records");
   static_assert(NR % RS == 0, "the ring divides the record's rows");
-  // RS: rows in flight per wave; K: groups of row output held per wave before a burst
+  // RS: rows per load block of a wave; K: groups of row output held per wave before a burst
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t* fold = lds + kRepDwords;  // [A4 | A8 | A12 | A16 | A32 | A48]
   const uint8_t* ldsb = reinterpret_cast<const uint8_t*>(lds);
@@ -1494,15 +1498,18 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
   const uint32_t L = p.fixed_len;  // == 64 * NR (host-checked)
 
   auto rec_idx = [&](uint32_t gg) { return (gg << 4) + (uint32_t)(lane >> 2); };
+  // (no short-circuit: the three compares are cheaper than the branches around them)
   auto is_live = [&](uint32_t i) {
     const uint64_t off = (uint64_t)i * p.stride;
-    return i < p.n && off <= p.slab_bytes && L <= p.slab_bytes - off;
+    return (bool)((i < p.n) & (off <= p.slab_bytes) & (L <= p.slab_bytes - off));
   };
   // lane's row base (32-bit offset, saddr form); a dead lane reads inside the slab at 64
-  auto row_base = [&](uint32_t gg) {
-    const uint32_t i = rec_idx(gg);
-    return (is_live(i) ? i * (uint32_t)p.stride : 64u) + 16u * (uint32_t)q;
+  auto row_base = [&](uint32_t i, bool live) {
+    return (live ? i * (uint32_t)p.stride : 64u) + 16u * (uint32_t)q;
   };
+  // quad lane q keeps dwords 2q, 2q + 1 of the record's row: lane masks, not branches
+  const uint32_t qm0 = 0u - (uint32_t)(q == 0), qm1 = 0u - (uint32_t)(q == 1);
+  const uint32_t qm2 = 0u - (uint32_t)(q == 2), qm3 = 0u - (uint32_t)(q == 3);
   auto ld = [&](uint32_t base, int j) { return ldu128(p.slab + (uint64_t)base + 64 * j); };
   auto decide = [&](const u32x4_t& pf, bool live) {
     const uint32_t w0 = prefix_word(pf, 0);
@@ -1547,14 +1554,14 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
       bc(err, h.err); bc(dtype, h.dst_type); bc(dlen, h.dst_len); bc(ptype, h.ptype);
       bc(gps, h.gps);
     }
-    if (!live) {
-      flow = seq = sec = usec = dst4 = msg_len = dport = plen = flags = dtype = dlen = 0;
-      ptype = gps = 0;
-      err = MGENX_ERROR_OOB;
-    }
-    o0 = q == 0 ? flow : q == 1 ? sec : q == 2 ? dst4 : (plen | flags << 16 | err << 24);
-    o1 = q == 0 ? seq : q == 1 ? usec : q == 2 ? (msg_len | dport << 16)
-                                              : (dtype | dlen << 8 | ptype << 16 | gps << 24);
+    const uint32_t a3 = plen | flags << 16 | err << 24;
+    const uint32_t c3 = dtype | dlen << 8 | ptype << 16 | gps << 24;
+    const uint32_t c2 = msg_len | dport << 16;
+    const uint32_t r0 = (flow & qm0) | (sec & qm1) | (dst4 & qm2) | (a3 & qm3);
+    const uint32_t r1 = (seq & qm0) | (usec & qm1) | (c2 & qm2) | (c3 & qm3);
+    // a dead lane: every field 0, err = OOB
+    o0 = live ? r0 : (qm3 & ((uint32_t)MGENX_ERROR_OOB << 24));
+    o1 = live ? r1 : 0u;
   };
   // the caller's receive check (mgenTransport.cpp:971): ERROR_CHECKSUM (+ TCP flag) in word 6
   auto verdict = [&](uint32_t& o0, bool crc_bad) {
@@ -1562,20 +1569,24 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
     if (crc_bad && q == 3) o0 = (o0 & 0x00ffffffu) | fl << 16 | (uint32_t)MGENX_ERROR_CHECKSUM << 24;
   };
 
-  // ---- output shift register: buf[K-1] = the newest group, `held` groups pending
-  uint32_t b0[K], b1[K];
-#pragma unroll
-  for (int k = 0; k < K; k++) b0[k] = b1[k] = 0u;
+  // ---- row output held per wave: slot k of buf, `held` groups pending.  A group's row goes
+  // to slot `slot` by a wave-uniform indexed move (no shift of the held rows); a burst's
+  // first slot is K - (groups in that burst), so at flush time slot k always belongs to
+  // group last_g - (K - 1 - k) * n_waves
+  typedef uint32_t held_t __attribute__((ext_vector_type(K)));
+  held_t b0 = 0u, b1 = 0u;
   uint32_t held = 0, last_g = 0;
+  // groups this wave still has to push (wave-uniform)
+  uint32_t left = __builtin_amdgcn_readfirstlane(
+      wave_id < g_end ? (g_end - 1u - wave_id) / n_waves + 1u : 0u);
+  uint32_t slot = (uint32_t)K - (left < (uint32_t)K ? left : (uint32_t)K);
   auto push = [&](uint32_t o0, uint32_t o1, uint32_t gg) {
-#pragma unroll
-    for (int k = 0; k < K - 1; k++) {
-      b0[k] = b0[k + 1];
-      b1[k] = b1[k + 1];
-    }
-    b0[K - 1] = o0;
-    b1[K - 1] = o1;
+    const uint32_t us = __builtin_amdgcn_readfirstlane(slot);  // one indexed move each
+    b0[us] = o0;
+    b1[us] = o1;
+    slot++;
     held++;
+    left--;
     last_g = gg;
   };
   auto flush = [&]() {  // buf[k] belongs to group last_g - (K - 1 - k) * n_waves
@@ -1591,14 +1602,17 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
                      : (uint64_t)p.sink + 8u * (uint32_t)lane, v);
     }
     held = 0;
+    slot = (uint32_t)K - (left < (uint32_t)K ? left : (uint32_t)K);
   };
 
   u32x4_t d[RS];
   uint32_t g = wave_id;
-  const uint32_t base0 = row_base(g < g_end ? g : 0u);
+  uint32_t idx = rec_idx(g < g_end ? g : 0u);
+  bool live = is_live(idx);
+  uint32_t base = row_base(idx, live);
 #pragma unroll
   for (int j = 0; j < RS; j++) {
-    d[j] = ld(base0, j);
+    d[j] = ld(base, j);
     __builtin_amdgcn_sched_barrier(0);
   }
   table_writes(lds, tab_regs);
@@ -1606,14 +1620,20 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
   __builtin_amdgcn_s_barrier();
   if (g >= g_end) return;
 
-  bool pipelined = true;
-  while (g < g_end) {
-    const uint32_t gn = g + n_waves;
-    const bool has_next = gn < g_end;
-    const uint32_t idx = rec_idx(g);
-    const bool live = is_live(idx);
-    if (pipelined) {
-      const uint32_t base = row_base(g), base_n = row_base(has_next ? gn : g);
+  // Two modes, each in its own loop.  The pipelined loop is the only place that redefines
+  // the ring inside a loop, and it does so in place (slot t % RS by row t + RS of the wave's
+  // row stream); the header-only loop never touches the ring, and the switch back re-primes
+  // it outside both.  (In one mixed loop the header-only path's second definition of the
+  // ring made LLVM copy the whole ring at the back edge, 16 moves per group.)
+  for (;;) {
+    // ---- pipelined groups: d[] holds rows 0 .. RS-1 of group g; idx, live, base are g's
+    bool more;
+    do {
+      const uint32_t gn = g + n_waves;
+      const bool has_next = gn < g_end;
+      const uint32_t idx_n = rec_idx(has_next ? gn : g);
+      const bool live_n = is_live(idx_n);
+      const uint32_t base_n = row_base(idx_n, live_n);
       const u32x4_t hdr = d[0];  // row 0 = the 64-byte header prefix (aligned)
       const bool needs_crc = decide(hdr, live);
       const bool any = __any(needs_crc);
@@ -1628,8 +1648,13 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
 #pragma unroll
         for (int b = 0; b < 4; b++) c4[b] = xor3(ha[b], hb[b], xw[b]);
         __builtin_amdgcn_sched_barrier(0);
-        // row j + RS of the stream: this group's row, or the next group's
-        d[j % RS] = (j + RS < NR) ? ld(base, j + RS) : ld(base_n, j + RS - NR);
+        // the block's last row is out of the ring: the next block of the stream (this group's
+        // rows, or the next group's first RS), back to back
+        if ((j % RS) == RS - 1) {
+#pragma unroll
+          for (int t = j - (RS - 1); t <= j; t++)
+            d[t % RS] = (t + RS < NR) ? ld(base, t + RS) : ld(base_n, t + RS - NR);
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 4; b++) a64_parts(ldsb, c4[b], s1, ha[b], hb[b]);
@@ -1640,7 +1665,8 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
       uint32_t f3 = xor3(ha[3], hb[3], q == 3 ? bswap32(xf.w) : xf.w);
       asm volatile("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3));
       __builtin_amdgcn_sched_barrier(0);
-      d[(NR - 1) % RS] = ld(base_n, NR - 1 + RS - NR);
+#pragma unroll
+      for (int t = NR - RS; t < NR; t++) d[t % RS] = ld(base_n, t + RS - NR);
       __builtin_amdgcn_sched_barrier(0);
       const uint32_t v = shift_tab(fold + 3 * 1024, f0) ^ shift_tab(fold + 2 * 1024, f1) ^
                          shift_tab(fold + 1 * 1024, f2) ^ shift_tab(fold, f3);
@@ -1650,25 +1676,30 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
       sum ^= __shfl_xor(sum, 2);
       verdict(o0, needs_crc && sum != expect);
       push(o0, o1, g);
-      asm volatile("" ::"v"(base_n));
-      pipelined = has_next && any;  // a group without checksummed records: header-only
-    } else {
-      // header-only mode: header first, body only when a record needs the CRC
-      const u32x4_t ph = ld(row_base(g), 0);
-      if (__any(decide(ph, live))) {
-        // back to the pipelined mode at this group: its first RS rows, then re-run it
-        const uint32_t bb = row_base(g);
-#pragma unroll
-        for (int j = 0; j < RS; j++) d[j] = ld(bb, j);
-        pipelined = true;
-        continue;
-      }
+      if (held == (uint32_t)K) flush();
+      g = gn;
+      idx = idx_n;
+      live = live_n;
+      base = base_n;
+      // a group without checksummed records: its successors run header-only (the rows of
+      // the next group in flight are simply overwritten later)
+      more = has_next && any;
+    } while (more);
+    // ---- header-only groups: header first, body only when a record needs the CRC
+    for (; g < g_end; g += n_waves) {
+      idx = rec_idx(g);
+      live = is_live(idx);
+      base = row_base(idx, live);
+      const u32x4_t ph = ld(base, 0);
+      if (__any(decide(ph, live))) break;
       uint32_t o0, o1;
       decode(ph, idx, live, o0, o1);
       push(o0, o1, g);
+      if (held == (uint32_t)K) flush();
     }
-    if (held == (uint32_t)K) flush();
-    g = gn;
+    if (g >= g_end) break;
+    // ---- back to the pipelined mode at group g: its first RS rows
+    for (int j = 0; j < RS; j++) d[j] = ld(base, j);
   }
   if (held) flush();
 }
