@@ -52,6 +52,8 @@ extern "C" {
 #define MGENX_EINVAL     -1   /* bad argument (null pointer, zero stride ...) */
 #define MGENX_EDEVICE    -2   /* HIP error (no device, launch failure) */
 #define MGENX_ENOMEM     -3   /* context workspace allocation failed (create only) */
+#define MGENX_ENOSPC     -4   /* a caller-given output window is too small: nothing was
+                                 written, the need is reported (mgenx_pcap_defrag) */
 
 /* ---- wire constants (include/mgenGlobals.h:70-80, include/mgenMsg.h:60-103) ---- */
 #define MGENX_MIN_SIZE        28
@@ -938,6 +940,80 @@ int mgenx_pcapng_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uin
                       const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
                       uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
                       void* stream);
+
+/* ---- pcap2mgen: reassembly of fragmented IPv4 / IPv6 datagrams (an option; the reference
+ * does not reassemble, and without this call nothing below happens) ----
+ * mgenx_pcap_defrag / mgenx_pcapng_defrag run after the parse (and after the snap step) over
+ * the same packets, in place.  A packet that is not a fragment is not touched.
+ *
+ * Which packets are fragments.  Only a packet whose status is not BAD_ETH / NOT_IP / BAD_IP /
+ * OOB is examined, by the link-layer and IP-header walk of the parse up to its protocol test
+ * (ip0 = the IP header's offset, num = min(caplen, 4094)):
+ *   IPv4: F = be16(ip0+6), MF = F & 0x2000, off = (F & 0x1FFF) * 8; a fragment iff MF || off;
+ *         protocol 17 only (another protocol stays NOT_UDP); id = be16(ip0+4); payload
+ *         [ip0+ihl, ip0+tot); key (4, src, dst, id).
+ *   IPv6: the fixed header's next header is 44 (only this position is opened); pl < 8 is
+ *         BAD_IP; the 8-byte fragment header at ip0+40 must lie inside num (else TRUNCATED):
+ *         byte 0 = the inner next header, 17 only (else NOT_UDP stays); off = be16(+2) &
+ *         0xFFF8, MF = be16(+2) & 1, id = be32(+4); payload [ip0+48, ip0+40+pl); an atomic
+ *         fragment (off 0, MF 0) is a fragment and completes on its own; key (6, src, dst, id).
+ *   Payload of len bytes, tested in this order: len == 0 -> BAD_IP; MF && len % 8 -> BAD_IP;
+ *         off + len > 65535 -> BAD_IP; not wholly inside num -> TRUNCATED.  Such a packet gets
+ *         that status, udp_len 0 and src.port 0 and takes no part in reassembly.
+ *
+ * The state machine, per key, over its valid fragments in capture order; t = the packet's
+ * receive time rx_sec * 10^6 + rx_usec as int64; at most one context is open per key.  On
+ * fragment p:
+ *   1. an open context with timeout_us > 0 and t - ctx.t0 > timeout_us is dropped (a negative
+ *      difference does not expire it);
+ *   2. an open context that p conflicts with is dropped: [off, off+len) intersects a held
+ *      fragment (an exact duplicate too); the total L is known and off+len > L; MF == 0 and L
+ *      is known; MF == 0 and off+len is below a held fragment's end; it holds 64 fragments;
+ *   3. with no context open, one opens with t0 = t;
+ *   4. p is added: sum += len; L = off+len when MF == 0; status[p] = MGENX_PCAP_FRAGMENT,
+ *      udp_len[p] = 0, src[p].port = 0;
+ *   5. with L known and sum == L the datagram is complete at p and the context closes.
+ * A dropped context, and one open at the end of the capture, is incomplete; its packets stay
+ * FRAGMENT.  (Dropping on overlap rather than ignoring the newcomer keeps a datagram that lost
+ * a fragment from splicing into the next one that reuses its id: DESIGN.md 4.10.)
+ *
+ * Completion at packet p over the L assembled bytes D: L < 8, or ul = be16(D+4) below 8 or
+ * above L: status[p] = NOT_UDP, udp_len[p] = 0.  Otherwise status[p] = MGENX_PCAP_UDP,
+ * udp_off[p] = the scratch position of D + 8, udp_len[p] = ul - 8, src[p].port = be16(D).
+ * Source address, ttl and receive time stay the completing packet's own.  The 4094-byte frame
+ * rule applies to each fragment's frame, not to the datagram.
+ *
+ * Scratch: dev_buf[scratch_off, buf_bytes), at or after the file image and any snap scratch;
+ * every packet must lie below scratch_off (one reaching past it is not examined).  Datagrams
+ * are laid out in order of their completing packet's index, each in a slot of round16(L)
+ * bytes whose pad bytes are zero (rejected datagrams too); dev_buf + scratch_off must be
+ * 16-byte aligned when anything is written.  stats (host memory) is always filled; the call is
+ * synchronous (one read-back of the sizes).  With a window smaller than stats->scratch_bytes no
+ * output array and no scratch byte is changed and MGENX_ENOSPC comes back: a call with an empty
+ * window sizes the scratch.  mgenx_pcap_defrag takes the records as mgenx_pcap_snap does;
+ * mgenx_pcapng_defrag takes the packet blocks (for each packet's original length) and the
+ * data_off / cap_len mgenx_pcapng_parse wrote (flags: MGENX_PCAP_SWAPPED as there). */
+#define MGENX_PCAP_FRAGMENT  8  /* status: a fragment of a datagram that did not complete here */
+#define MGENX_DEFRAG_MAX_FRAGS 64
+typedef struct {
+    uint64_t n_fragments;    /* valid fragments that entered the state machine */
+    uint64_t n_datagrams;    /* datagrams completed */
+    uint64_t n_not_udp;      /* completed datagrams rejected as UDP */
+    uint64_t n_incomplete;   /* contexts dropped, expired or open at the end */
+    uint64_t scratch_bytes;  /* the exact need: sum of round16(L) over completed datagrams */
+} mgenx_defrag_stats;
+int mgenx_pcap_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                      const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                      int64_t timeout_us, const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream);
+int mgenx_pcapng_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                        uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                        const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                        uint32_t link_type, uint32_t flags, int64_t timeout_us,
+                        const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                        uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                        mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream);
 
 /* ---- MgenMsg::ConvertBinaryLog: binary log -> text log (src/common/mgenMsg.cpp:1417-1900) --
  * mgenx_binlog_index (HOST memory, no device work) checks the header line ("mgen

@@ -28,11 +28,17 @@ struct PcapOptions {
   bool log_rx = true;      // +rxlog on|off
   bool epoch = false;      // Mgen::SetEpochTimestamp
   double window = 1.0;     // +window (MgenAnalytic::DEFAULT_WINDOW)
+  // not in the reference: rebuild fragmented IPv4 / IPv6 datagrams (mgenx_pcap_defrag)
+  bool reassemble = false;
+  double frag_timeout = 30.0;  // seconds a datagram may take to complete; 0 = no limit
 };
 
 class Pcap2Mgen {
  public:
   Pcap2Mgen(Context& ctx, const PcapOptions& o) : ctx_(ctx), o_(o) {}
+
+  // what the last run with PcapOptions::reassemble found (zeros before one)
+  const mgenx_defrag_stats& defrag_stats() const { return defrag_stats_; }
 
   // The log text of a pcap or pcapng file image (host memory); the first four bytes tell which
   // (a Section Header Block's type reads 0A 0D 0D 0A in either byte order).
@@ -47,21 +53,28 @@ class Pcap2Mgen {
     const uint32_t n = (uint32_t)info.n_records;
     if (n == 0) return std::string();
     hipStream_t s = ctx_.stream();
-    // the file image, then scratch for the packets a snapshot length cut (mgenx_pcap_snap)
-    DeviceArray<uint8_t> buf(nbytes + info.snap_bytes);
+    // the file image, then scratch for the packets a snapshot length cut (mgenx_pcap_snap),
+    // then, with reassemble, scratch for the rebuilt datagrams
+    const uint64_t defrag_off = DefragOff(nbytes + info.snap_bytes);
+    const uint64_t total = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    DeviceArray<uint8_t> buf(total);
     DeviceArray<uint64_t> pkt(n);
     check_hip(hipMemcpyAsync(buf.data(), file, nbytes, hipMemcpyHostToDevice, s), "H2D file");
     check_hip(hipMemcpyAsync(pkt.data(), offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, s),
               "H2D offsets");
     std::string out = RunDevice(buf.data(), nbytes, pkt.data(), n, info.link_type, info.flags,
-                                nbytes + info.snap_bytes);
+                                total, defrag_off);
     return out;
   }
 
   // The pipeline over a resident file image (device pointers).  buf_bytes > nbytes: scratch
-  // after the image for packets cut by the snapshot length (else they are skipped).
+  // after the image for packets cut by the snapshot length (else they are skipped).  With
+  // PcapOptions::reassemble the defrag scratch is [defrag_off, buf_bytes) (16-byte aligned; the
+  // file's size is always enough: a fragment's payload is shorter than its record) and the snap
+  // scratch ends there; defrag_off 0: no defrag scratch, a capture that needs some throws.
   std::string RunDevice(uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_pkt, uint32_t n,
-                        uint32_t link_type, uint32_t flags, uint64_t buf_bytes = 0) {
+                        uint32_t link_type, uint32_t flags, uint64_t buf_bytes = 0,
+                        uint64_t defrag_off = 0) {
     mgenx_ctx* c = ctx_.get();
     hipStream_t s = ctx_.stream();
     DeviceArray<uint64_t> udp_off(n);
@@ -73,12 +86,18 @@ class Pcap2Mgen {
                                 udp_len.data(), src.data(), ttl.data(), rx_sec.data(),
                                 rx_usec.data(), status.data(), s),
                "mgenx_pcap_parse");
-    if (buf_bytes > nbytes) {
-      ctx_.Check(mgenx_pcap_snap(c, d_buf, nbytes, buf_bytes, d_pkt, n, flags, status.data(),
+    if (buf_bytes < nbytes) buf_bytes = nbytes;
+    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : buf_bytes;
+    if (snap_end > nbytes)
+      ctx_.Check(mgenx_pcap_snap(c, d_buf, nbytes, snap_end, d_pkt, n, flags, status.data(),
                                  udp_off.data(), udp_len.data(), s),
                  "mgenx_pcap_snap");
-      nbytes = buf_bytes;  // the records now reach into the scratch
-    }
+    if (o_.reassemble)
+      Defragged(mgenx_pcap_defrag(c, d_buf, snap_end, buf_bytes, d_pkt, n, link_type, flags,
+                                  FragTimeoutUs(), rx_sec.data(), rx_usec.data(), status.data(),
+                                  udp_off.data(), udp_len.data(), src.data(), &defrag_stats_, s),
+                buf_bytes - snap_end);
+    nbytes = buf_bytes;  // the records may now reach into the scratch
     return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
   }
 
@@ -87,7 +106,7 @@ class Pcap2Mgen {
   std::string RunDeviceNg(uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_pkt,
                           const uint32_t* d_pkt_if, uint32_t n, const mgenx_pcapng_if* d_ifaces,
                           uint32_t n_ifaces, uint32_t link_type, uint32_t flags,
-                          uint64_t buf_bytes = 0) {
+                          uint64_t buf_bytes = 0, uint64_t defrag_off = 0) {
     mgenx_ctx* c = ctx_.get();
     hipStream_t s = ctx_.stream();
     DeviceArray<uint64_t> udp_off(n), data_off(n);
@@ -100,12 +119,19 @@ class Pcap2Mgen {
                                   ttl.data(), rx_sec.data(), rx_usec.data(), status.data(),
                                   data_off.data(), cap_len.data(), s),
                "mgenx_pcapng_parse");
-    if (buf_bytes > nbytes) {
-      ctx_.Check(mgenx_pcapng_snap(c, d_buf, nbytes, buf_bytes, data_off.data(), cap_len.data(),
+    if (buf_bytes < nbytes) buf_bytes = nbytes;
+    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : buf_bytes;
+    if (snap_end > nbytes)
+      ctx_.Check(mgenx_pcapng_snap(c, d_buf, nbytes, snap_end, data_off.data(), cap_len.data(),
                                    n, status.data(), udp_off.data(), udp_len.data(), s),
                  "mgenx_pcapng_snap");
-      nbytes = buf_bytes;
-    }
+    if (o_.reassemble)
+      Defragged(mgenx_pcapng_defrag(c, d_buf, snap_end, buf_bytes, d_pkt, data_off.data(),
+                                    cap_len.data(), n, link_type, flags, FragTimeoutUs(),
+                                    rx_sec.data(), rx_usec.data(), status.data(), udp_off.data(),
+                                    udp_len.data(), src.data(), &defrag_stats_, s),
+                buf_bytes - snap_end);
+    nbytes = buf_bytes;
     return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
   }
 
@@ -123,7 +149,9 @@ class Pcap2Mgen {
     const uint32_t n = (uint32_t)info.n_records;
     if (n == 0) return std::string();
     hipStream_t s = ctx_.stream();
-    DeviceArray<uint8_t> buf(nbytes + info.snap_bytes);
+    const uint64_t defrag_off = DefragOff(nbytes + info.snap_bytes);
+    const uint64_t total = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    DeviceArray<uint8_t> buf(total);
     DeviceArray<uint64_t> pkt(n);
     DeviceArray<uint32_t> pkt_if(n);
     DeviceArray<mgenx_pcapng_if> d_ifs(info.n_ifaces);
@@ -137,7 +165,23 @@ class Pcap2Mgen {
                              hipMemcpyHostToDevice, s),
               "H2D interface table");
     return RunDeviceNg(buf.data(), nbytes, pkt.data(), pkt_if.data(), n, d_ifs.data(),
-                       info.n_ifaces, info.link_type, info.flags, nbytes + info.snap_bytes);
+                       info.n_ifaces, info.link_type, info.flags, total, defrag_off);
+  }
+
+  // where Run puts the defrag scratch: 16-byte aligned after the snap scratch (0: none)
+  uint64_t DefragOff(uint64_t used) const {
+    return o_.reassemble ? (used + 15) & ~(uint64_t)15 : 0;
+  }
+
+  int64_t FragTimeoutUs() const {
+    return o_.frag_timeout > 0.0 ? (int64_t)std::llround(o_.frag_timeout * 1e6) : 0;
+  }
+
+  void Defragged(int rc, uint64_t window) {
+    if (rc == MGENX_ENOSPC)
+      throw Error("pcap2mgen: reassembly needs " + std::to_string(defrag_stats_.scratch_bytes) +
+                  " bytes of scratch, the buffer has " + std::to_string(window));
+    ctx_.Check(rc, "mgenx_pcap_defrag");
   }
 
   // everything after the frame walk (either format): Unpack, analytics, the log lines
@@ -337,6 +381,7 @@ class Pcap2Mgen {
 
   Context& ctx_;
   PcapOptions o_;
+  mgenx_defrag_stats defrag_stats_ = {};
 };
 
 }  // namespace mgenx

@@ -29,6 +29,7 @@ from ._abi import (  # noqa: F401
     PCAP_NG, PcapngInfo, PCAPNG_IF_DTYPE, PCAPNG_OK, PCAPNG_TRUNCATED, PCAPNG_BLOCK,
     PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE, PCAPNG_TSRESOL, PCAPNG_CAPLEN,
     FLOW_DIST_BINS, FLOW_DIST_DTYPE,
+    ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcapng_index", "mgenx_pcapng_parse", "mgenx_pcapng_snap",
     "mgenx_flow_dist_init", "mgenx_flow_dist", "mgenx_flow_dist_quantiles",
     "mgenx_flow_dist_bin", "mgenx_flow_dist_bin_lo",
+    "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -120,6 +122,10 @@ def load(diag: bool = False):
     L.mgenx_pcapng_parse.argtypes = [P, P, u64, P, P, u32, P, u32, u32, u32, P, P, P, P, P, P, P,
                                      P, P, P]
     L.mgenx_pcapng_snap.argtypes = [P, P, u64, u64, P, P, u32, P, P, P, P]
+    L.mgenx_pcap_defrag.argtypes = [P, P, u64, u64, P, u32, u32, u32, ctypes.c_int64, P, P, P, P,
+                                    P, P, ctypes.POINTER(DefragStats), P]
+    L.mgenx_pcapng_defrag.argtypes = [P, P, u64, u64, P, P, P, u32, u32, u32, ctypes.c_int64, P,
+                                      P, P, P, P, P, ctypes.POINTER(DefragStats), P]
     L.mgenx_binlog_index.argtypes = [P, u64, P, u64, ctypes.POINTER(BinlogInfo)]
     L.mgenx_convert_binary_log.argtypes = [P, P, u64, P, u32, u32, u32, P, u64, P, P]
     L.mgenx_text_index.argtypes = [P, P, u64, P, u64, P, P]
@@ -730,10 +736,11 @@ class Engine:
                     "mgenx_pcap_parse")
         return o
 
-    def pcap_snap(self, buf, file_bytes, pkt_off, n, flags, parsed):
+    def pcap_snap(self, buf, file_bytes, pkt_off, n, flags, parsed, buf_bytes=None):
         """mgenx_pcap_snap: move the SNAPPED packets of `parsed` (pcap_parse's dict) into
-        buf[file_bytes:], zero-extended, in place."""
-        self._check(self.lib.mgenx_pcap_snap(self.ctx, _ptr(buf), file_bytes, buf.numel(),
+        buf[file_bytes:buf_bytes] (default: to the end of buf), zero-extended, in place."""
+        self._check(self.lib.mgenx_pcap_snap(self.ctx, _ptr(buf), file_bytes,
+                                             buf.numel() if buf_bytes is None else buf_bytes,
                                              _ptr(pkt_off), n, flags, _ptr(parsed["status"]),
                                              _ptr(parsed["udp_off"]), _ptr(parsed["udp_len"]),
                                              _stream(self.device)), "mgenx_pcap_snap")
@@ -762,15 +769,47 @@ class Engine:
             _ptr(o["data_off"]), _ptr(o["cap_len"]), _stream(self.device)), "mgenx_pcapng_parse")
         return o
 
-    def pcapng_snap(self, buf, file_bytes, n, parsed):
+    def pcapng_snap(self, buf, file_bytes, n, parsed, buf_bytes=None):
         """mgenx_pcapng_snap: move the SNAPPED packets of `parsed` (pcapng_parse's dict) into
-        buf[file_bytes:], zero-extended, in place."""
-        self._check(self.lib.mgenx_pcapng_snap(self.ctx, _ptr(buf), file_bytes, buf.numel(),
+        buf[file_bytes:buf_bytes] (default: to the end of buf), zero-extended, in place."""
+        self._check(self.lib.mgenx_pcapng_snap(self.ctx, _ptr(buf), file_bytes,
+                                               buf.numel() if buf_bytes is None else buf_bytes,
                                                _ptr(parsed["data_off"]), _ptr(parsed["cap_len"]),
                                                n, _ptr(parsed["status"]), _ptr(parsed["udp_off"]),
                                                _ptr(parsed["udp_len"]), _stream(self.device)),
                     "mgenx_pcapng_snap")
         return parsed
+
+    def pcap_defrag(self, buf, scratch_off, pkt_off, n, link_type, flags, parsed,
+                    timeout_us=30_000_000):
+        """mgenx_pcap_defrag: reassemble the fragmented datagrams of `parsed` (pcap_parse's
+        dict, after pcap_snap) into buf[scratch_off:], in place.  Returns (fits, DefragStats):
+        fits False = the window is smaller than stats.scratch_bytes and nothing was changed
+        (an empty window sizes the scratch).  Synchronous."""
+        st = DefragStats()
+        rc = self.lib.mgenx_pcap_defrag(
+            self.ctx, _ptr(buf), scratch_off, buf.numel(), _ptr(pkt_off), n, link_type, flags,
+            int(timeout_us), _ptr(parsed["rx_sec"]), _ptr(parsed["rx_usec"]),
+            _ptr(parsed["status"]), _ptr(parsed["udp_off"]), _ptr(parsed["udp_len"]),
+            _ptr(parsed["src"]), ctypes.byref(st), _stream(self.device))
+        if rc != ENOSPC:
+            self._check(rc, "mgenx_pcap_defrag")
+        return rc == 0, st
+
+    def pcapng_defrag(self, buf, scratch_off, pkt_off, n, link_type, flags, parsed,
+                      timeout_us=30_000_000):
+        """mgenx_pcapng_defrag: pcap_defrag for pcapng packets (pkt_off: the packet blocks,
+        `parsed`: pcapng_parse's dict with data_off and cap_len)."""
+        st = DefragStats()
+        rc = self.lib.mgenx_pcapng_defrag(
+            self.ctx, _ptr(buf), scratch_off, buf.numel(), _ptr(pkt_off),
+            _ptr(parsed["data_off"]), _ptr(parsed["cap_len"]), n, link_type, flags,
+            int(timeout_us), _ptr(parsed["rx_sec"]), _ptr(parsed["rx_usec"]),
+            _ptr(parsed["status"]), _ptr(parsed["udp_off"]), _ptr(parsed["udp_len"]),
+            _ptr(parsed["src"]), ctypes.byref(st), _stream(self.device))
+        if rc != ENOSPC:
+            self._check(rc, "mgenx_pcapng_defrag")
+        return rc == 0, st
 
     def flow_export(self, flows, n_flows, out=None):
         if out is None:

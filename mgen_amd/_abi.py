@@ -187,6 +187,20 @@ class PcapngInfo(ctypes.Structure):    # mgenx_pcapng_info
                 ("n_sections", ctypes.c_uint32)]
 
 
+ENOSPC = -4               # MGENX_ENOSPC
+PCAP_FRAGMENT = 8         # MGENX_PCAP_FRAGMENT
+DEFRAG_MAX_FRAGS = 64     # MGENX_DEFRAG_MAX_FRAGS
+
+
+class DefragStats(ctypes.Structure):   # mgenx_defrag_stats
+    _fields_ = [("n_fragments", ctypes.c_uint64), ("n_datagrams", ctypes.c_uint64),
+                ("n_not_udp", ctypes.c_uint64), ("n_incomplete", ctypes.c_uint64),
+                ("scratch_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BinlogInfo(ctypes.Structure):    # mgenx_binlog_info
     _fields_ = [("n_records", ctypes.c_uint64), ("consumed", ctypes.c_uint64),
                 ("status", ctypes.c_int32), ("version", ctypes.c_uint32)]

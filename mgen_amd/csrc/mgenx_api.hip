@@ -93,6 +93,16 @@ extern "C" int mgenx_pcap_snap_run(uint8_t* dev_buf, uint64_t file_bytes, uint64
                                    uint64_t* dev_udp_off, uint32_t* dev_udp_len, uint64_t* need,
                                    void* scan_tmp, size_t scan_bytes, hipStream_t stream);
 extern "C" size_t mgenx_pcap_snap_scan_bytes(uint32_t n);
+extern "C" size_t mgenx_defrag_ws(uint32_t n);
+extern "C" int mgenx_defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off,
+                                uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                                const uint64_t* dev_data_off, const uint32_t* dev_cap_len,
+                                uint32_t n, uint32_t link_type, uint32_t flags,
+                                int64_t timeout_us, const uint32_t* dev_rx_sec,
+                                const uint32_t* dev_rx_usec, uint8_t* dev_status,
+                                uint64_t* dev_udp_off, uint32_t* dev_udp_len, mgenx_addr* dev_src,
+                                mgenx_defrag_stats* stats, hipStream_t stream, char* err,
+                                size_t errn);
 extern "C" int mgenx_log_recv_run(void* ws, bool binary, const uint8_t* slab,
                                   uint64_t slab_bytes, const uint64_t* rec_off,
                                   const uint32_t* rec_len,
@@ -205,6 +215,7 @@ struct mgenx_ctx {
   int pack_variant = 0;
   mgenx_grow bl[5];                // mgenx_convert_binary_log: records, lines, pairs, report text
   mgenx_grow snap;                 // mgenx_pcap_snap: per-packet sizes + scan scratch
+  mgenx_grow defrag;               // mgenx_pcap_defrag: per-packet arrays + sort / scan scratch
   mgenx_grow lp;                   // mgenx_text_index / mgenx_log_parse_text: per-line scratch
   bool rand_ready = false;
   uint32_t rand_time = 0;
@@ -400,6 +411,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   mgenx::host_free(c->tcp_host);
   for (mgenx_grow& g : c->bl) g.release();
   c->snap.release();
+  c->defrag.release();
   c->lp.release();
   for (void* p : ps) mgenx::dev_free(p);
   delete c;
@@ -1601,6 +1613,52 @@ int mgenx_pcapng_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uin
   if (n && !dev_cap_len) return MGENX_EINVAL;
   return pcap_snap_any(ctx, dev_buf, file_bytes, buf_bytes, dev_data_off, dev_cap_len, n, 0,
                        dev_status, dev_udp_off, dev_udp_len, stream);
+}
+
+// both defrags: dev_data_off null = classic records at dev_pkt_off, else pcapng packet blocks
+static int pcap_defrag_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                           uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                           const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                           uint32_t link_type, uint32_t flags, int64_t timeout_us,
+                           const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                           uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                           mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  if (!ctx || !stats || buf_bytes < scratch_off || n > 0x7FFFFFFEu) return MGENX_EINVAL;
+  memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_rx_sec || !dev_rx_usec || !dev_status || !dev_udp_off ||
+      !dev_udp_len || !dev_src)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  void* m = ctx->defrag.get(mgenx_defrag_ws(n));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_defrag workspace");
+  return mgenx_defrag_run(m, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                          dev_cap_len, n, link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec,
+                          dev_status, dev_udp_off, dev_udp_len, dev_src, stats,
+                          (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_pcap_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                      const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                      int64_t timeout_us, const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  return pcap_defrag_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, nullptr, nullptr, n,
+                         link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec, dev_status,
+                         dev_udp_off, dev_udp_len, dev_src, stats, stream);
+}
+
+int mgenx_pcapng_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                        uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                        const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                        uint32_t link_type, uint32_t flags, int64_t timeout_us,
+                        const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                        uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                        mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  if (n && (!dev_data_off || !dev_cap_len)) return MGENX_EINVAL;
+  return pcap_defrag_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                         dev_cap_len, n, link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec,
+                         dev_status, dev_udp_off, dev_udp_len, dev_src, stats, stream);
 }
 
 // ---- ConvertBinaryLog (mgenMsg.cpp:1417-1900) ----

@@ -13,6 +13,10 @@ Here the whole file goes to HBM once and every stage is one batch call of the C 
   (MGENX_LOG_SKIP_ERR) -> mgenx_data_walk + mgenx_log_report_recv_text ->
   mgenx_text_interleave (per packet: analytic REPORT, RECV, received REPORTs).
 
+``reassemble`` (not in the reference, off by default) adds mgenx_pcap_defrag /
+mgenx_pcapng_defrag after the snap step: fragmented IPv4 / IPv6 datagrams are rebuilt in
+scratch after the file image and logged at their completing fragment's position.
+
 Options mirror the reference's command line (``-analytic``/``-report``, ``+rxlog on|off``,
 ``+window``); ``trace`` (MAC addresses in front of each line) is not supported.
 """
@@ -49,8 +53,12 @@ class Pcap2Mgen:
     FIRST_FLOWS = 65536  # flow-table capacity tried first (see run_device)
 
     def __init__(self, engine: Engine, analytics: bool = False, log_rx: bool = True,
-                 window: float = 1.0, epoch: bool = False):
+                 window: float = 1.0, epoch: bool = False, reassemble: bool = False,
+                 frag_timeout: float = 30.0):
         self.eng = engine
+        self.reassemble = reassemble
+        self.frag_timeout = frag_timeout      # seconds; 0 = fragments never expire
+        self.last_defrag_stats = None         # DefragStats of the last reassembling run
         self.analytics = analytics
         self.log_rx = log_rx
         self.window = window
@@ -60,7 +68,9 @@ class Pcap2Mgen:
         """Host index walk + one H2D copy: (device file, device record offsets, PcapInfo).
         A pcapng capture (told by its first four bytes): the offsets are its packet blocks,
         the info is a PcapngInfo with two more attributes for run_device's `ng`, pkt_if and
-        ifaces (device tensors: each packet's interface row, the interface table)."""
+        ifaces (device tensors: each packet's interface row, the interface table).
+        With reassemble the buffer also holds the defrag scratch, from info.defrag_off on:
+        as many bytes as the file (each fragment's payload is shorter than its record)."""
         torch = self.eng.torch
         b = np.frombuffer(bytes(file), np.uint8) if not isinstance(file, np.ndarray) else file
         dev = f"cuda:{self.eng.device}"
@@ -71,41 +81,59 @@ class Pcap2Mgen:
         else:
             offs, info = pcap_index(b)
         # the file image, then scratch for packets cut by the snapshot length (mgenx_pcap_snap)
-        buf = torch.zeros(b.size + int(info.snap_bytes), dtype=torch.uint8, device=dev)
+        size = b.size + int(info.snap_bytes)
+        info.file_bytes = b.size
+        info.defrag_off = None
+        if self.reassemble:
+            info.defrag_off = (size + 15) & ~15
+            size = info.defrag_off + b.size
+        buf = torch.zeros(size, dtype=torch.uint8, device=dev)
         buf[:b.size] = torch.from_numpy(b.copy()).to(dev)
         pkt_off = torch.from_numpy(offs.view(np.int64).copy()).to(dev)
         return buf, pkt_off, info
 
     def run(self, file) -> bytes:
         buf, pkt_off, info = self.upload(file)
-        file_bytes = buf.numel() - int(info.snap_bytes)
+        file_bytes = info.file_bytes
         ng = (info.pkt_if, info.ifaces) if info.flags & PCAP_NG else None
         text, _ = self.run_device(buf, pkt_off, int(info.n_records), info.link_type, info.flags,
-                                  file_bytes=file_bytes, ng=ng)
+                                  file_bytes=file_bytes, ng=ng, defrag_off=info.defrag_off)
         return text.cpu().numpy().tobytes()
 
-    def run_device(self, buf, pkt_off, n, link_type, flags, file_bytes=None, ng=None):
+    def run_device(self, buf, pkt_off, n, link_type, flags, file_bytes=None, ng=None,
+                   defrag_off=None):
         """The device pipeline over a resident file: (text tensor, per-packet offsets).
         file_bytes: the file image's size when buf has scratch after it for snapped packets
         (None: no scratch; packets cut by the snapshot length are skipped).
         ng: for a pcapng capture, (pkt_if, ifaces) on the device -- pkt_off then holds the
-        packet blocks' offsets (mgenx_pcapng_index)."""
+        packet blocks' offsets (mgenx_pcapng_index).
+        defrag_off: with reassemble, where the defrag scratch starts in buf (the snap scratch
+        then ends there); None: no scratch, and a capture with fragments to rebuild raises."""
         eng, torch = self.eng, self.eng.torch
         dev = buf.device
         if n == 0:
             return torch.empty(0, dtype=torch.uint8, device=dev), torch.zeros(
                 1, dtype=torch.int64, device=dev)
-        snap = file_bytes is not None and file_bytes < buf.numel()
+        snap_end = buf.numel() if defrag_off is None else defrag_off
+        snap = file_bytes is not None and file_bytes < snap_end
         if ng is not None:
             pkt_if, ifaces = ng
             p = eng.pcapng_parse(buf, pkt_off, pkt_if, n, ifaces, ifaces.numel() // 24,
                                  link_type, flags)
             if snap:
-                eng.pcapng_snap(buf, file_bytes, n, p)
+                eng.pcapng_snap(buf, file_bytes, n, p, buf_bytes=snap_end)
         else:
             p = eng.pcap_parse(buf, pkt_off, n, link_type, flags)
             if snap:
-                eng.pcap_snap(buf, file_bytes, pkt_off, n, flags, p)
+                eng.pcap_snap(buf, file_bytes, pkt_off, n, flags, p, buf_bytes=snap_end)
+        if self.reassemble:
+            defrag = eng.pcap_defrag if ng is None else eng.pcapng_defrag
+            fits, st = defrag(buf, snap_end, pkt_off, n, link_type, flags, p,
+                              timeout_us=round(self.frag_timeout * 1e6))
+            self.last_defrag_stats = st
+            if not fits:
+                raise MgenxError(f"pcap2mgen: reassembly needs {st.scratch_bytes} bytes of "
+                                 f"scratch, the buffer has {buf.numel() - snap_end}")
         cols = eng.unpack(buf, n, rec_off=p["udp_off"], rec_len=p["udp_len"], opts=OPT_SKIP_CRC,
                           ext=True)
         sources = []
@@ -189,11 +217,13 @@ class Pcap2Mgen:
         return max(1, min(most, by_time))
 
 
-def pcap2mgen(file, analytics=False, log_rx=True, window=1.0, epoch=False, device=0) -> bytes:
+def pcap2mgen(file, analytics=False, log_rx=True, window=1.0, epoch=False, device=0,
+              reassemble=False, frag_timeout=30.0) -> bytes:
     """One-shot helper: the log text of a pcap or pcapng file image."""
     eng = Engine(device)
     try:
-        return Pcap2Mgen(eng, analytics, log_rx, window, epoch).run(file)
+        return Pcap2Mgen(eng, analytics, log_rx, window, epoch, reassemble,
+                         frag_timeout).run(file)
     finally:
         eng.close()
 

@@ -8,7 +8,11 @@
 // The whole capture is read, decoded on the device by mgenx::Pcap2Mgen
 // (include/mgenx_pcap.hpp) and the log written in one piece.  "trace" (MAC addresses in
 // front of each line) is not supported and is reported as such; "flush" has nothing to do
-// here.  Extra: "epoch" selects epoch timestamps (Mgen::SetEpochTimestamp).
+// here.  Extra: "epoch" selects epoch timestamps (Mgen::SetEpochTimestamp); "reassemble"
+// rebuilds fragmented IPv4 / IPv6 datagrams (the reference skips their fragments) and
+// "fragtime <sec>" sets how long a datagram may take to complete (default 30, 0 = no limit).
+// The two are matched after the commands above, so every prefix that named one of those
+// ("re" is report, "f" is flush) still does.
 #include <ctype.h>
 #include <stdio.h>
 #include <string.h>
@@ -23,23 +27,31 @@ namespace {
 enum CmdType { CMD_INVALID, CMD_ARG, CMD_NOARG };
 const char* const kCmds[] = {"-report", "-analytic", "+infile", "+outfile", "-trace",
                              "+rxlog",  "-flush",    "+window", "-epoch",   nullptr};
+const char* const kDefragCmds[] = {"-reassemble", "+fragtime", nullptr};
 
-// GetCmdType (:71-109): a unique case-insensitive prefix match
-CmdType GetCmdType(const char* cmd, const char** which) {
-  if (!cmd) return CMD_INVALID;
-  std::string low;
-  for (const char* p = cmd; *p && low.size() < 31; p++) low += (char)tolower(*p);
+// GetCmdType (:71-109): a unique case-insensitive prefix match, in one table
+CmdType MatchCmd(const char* const* table, const std::string& low, const char** which,
+                 bool* matched) {
   CmdType type = CMD_INVALID;
-  bool matched = false;
-  for (const char* const* c = kCmds; *c; c++) {
+  for (const char* const* c = table; *c; c++) {
     if (!strncmp(low.c_str(), *c + 1, low.size())) {
-      if (matched) return CMD_INVALID;  // ambiguous
-      matched = true;
+      if (*matched) return CMD_INVALID;  // ambiguous
+      *matched = true;
       type = ('+' == (*c)[0]) ? CMD_ARG : CMD_NOARG;
       *which = *c + 1;
     }
   }
   return type;
+}
+
+CmdType GetCmdType(const char* cmd, const char** which) {
+  if (!cmd) return CMD_INVALID;
+  std::string low;
+  for (const char* p = cmd; *p && low.size() < 31; p++) low += (char)tolower(*p);
+  bool matched = false;
+  const CmdType type = MatchCmd(kCmds, low, which, &matched);
+  if (matched) return type;
+  return MatchCmd(kDefragCmds, low, which, &matched);
 }
 
 bool ReadAll(FILE* f, std::vector<uint8_t>& out) {
@@ -99,6 +111,15 @@ int main(int argc, char* argv[]) {
         opt.window = w;
     } else if (!strcmp(which, "epoch")) {
       opt.epoch = true;
+    } else if (!strcmp(which, "reassemble")) {
+      opt.reassemble = true;
+    } else if (!strcmp(which, "fragtime")) {
+      double v;
+      if (1 != sscanf(val, "%lf", &v) || v < 0.0) {
+        fprintf(stderr, "pcap2mgen OnCommand Error: wrong argument to fragtime: %s\n", val);
+        return -1;
+      }
+      opt.frag_timeout = v;
     }  // flush: nothing to do
     i += (t == CMD_ARG) ? 2 : 1;
   }
@@ -111,6 +132,13 @@ int main(int argc, char* argv[]) {
     mgenx::Context ctx(0);
     mgenx::Pcap2Mgen p(ctx, opt);
     const std::string log = p.Run(file.data(), file.size());
+    const mgenx_defrag_stats& ds = p.defrag_stats();
+    if (opt.reassemble && ds.n_incomplete > 0)
+      fprintf(stderr,
+              "pcap2mgen: reassembly: %llu fragments, %llu datagrams (%llu not UDP), "
+              "%llu incomplete\n",
+              (unsigned long long)ds.n_fragments, (unsigned long long)ds.n_datagrams,
+              (unsigned long long)ds.n_not_udp, (unsigned long long)ds.n_incomplete);
     if (!log.empty() && fwrite(log.data(), 1, log.size(), outfile) != log.size()) {
       perror("pcap2mgen: write error");
       return -1;
