@@ -23,7 +23,9 @@ extern "C" {
  * cache policy, 32 = stores wrapped onto the first 16K records, 64 = write-through stores,
  * 128 = non-temporal row loads, 256 (with 4) = dummy rows stored after each wave's last
  * group), 40-45 = long-record kernel shapes (rows per block x threads: 16x512, 8x512,
- * 4x1024, 12x512, 2x1024, 16x1024). */
+ * 4x1024, 12x512, 2x1024, 16x1024), 17-32 = ring-kernel shapes on fixed 512/1024-B records
+ * with row output (waves per workgroup, rows per block, blocks, groups held; 27-32 with
+ * non-temporal loads: the table in launch_unpack, timed by scripts/ring_shapes.py). */
 #define MGENX_TUNE_UNPACK_VARIANT 1
 /* MGENX_TUNE_PACK_VARIANT: 0 = product; ablations 1 = no unit stores, 2 = no CRC work, 3-6
  * store-scheme ablations, 7-9 = grid x2..x4, 10 = the meta waves never help the joint

@@ -450,7 +450,8 @@ int mgenx_unpack_batch(mgenx_ctx* ctx, const uint8_t* dev_slab, uint64_t slab_by
   const uint64_t per_block = (uint64_t)mgenx::unpack_threads() / 64;  // waves per block
   uint64_t grid = (groups + per_block - 1) / per_block;
   if (grid > (uint64_t)ctx->cu_count) grid = ctx->cu_count;
-  hipError_t e = mgenx::launch_unpack(p, (int)grid, (hipStream_t)stream, &ctx->unpack_last);
+  hipError_t e = mgenx::launch_unpack(p, (int)grid, ctx->cu_count, (hipStream_t)stream,
+                                      &ctx->unpack_last);
   return e == hipSuccess ? MGENX_OK : set_err(ctx, e, "unpack");
 }
 

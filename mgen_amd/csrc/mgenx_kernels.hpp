@@ -94,7 +94,10 @@ struct PackParams {
                                    // verdict on a launch made before the host has read it)
 };
 
-hipError_t launch_unpack(const UnpackParams& p, int grid, hipStream_t stream, int* which);
+// grid: workgroups of unpack_threads() threads, one group per wave at least, at most `cus`;
+// the ring kernel (its own wave count per workgroup) sizes its grid from `cus` by the same rule
+hipError_t launch_unpack(const UnpackParams& p, int grid, int cus, hipStream_t stream,
+                         int* which);
 // tuning knob (mgenx_set_tuning): 0 = auto (pipelined fixed-length kernel when the batch
 // qualifies), 1/2 = ablations of the general kernel, 3 = general kernel only
 int unpack_threads();

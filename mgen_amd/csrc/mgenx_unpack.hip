@@ -70,29 +70,42 @@ __device__ __forceinline__ void a64_parts(const uint8_t* ldsb, uint32_t c, uint3
 
 // Stage the replicated A_64 tables (tabs[0..1023] = table k entry v at k * 256 + v) and the
 // fold tables (tabs[1024..]) into LDS, in two halves so a caller can put other loads in
-// flight between them: table_loads() reads this thread's entries (1024-thread blocks:
-// one A_64 entry and six fold entries), table_writes() stores them.  Caller synchronises.
+// flight between them: table_loads() reads this thread's entries (a workgroup of NT threads:
+// 1024 / NT A_64 entries and six times as many fold entries, entry e = thread + i * NT),
+// table_writes() stores them.  Caller synchronises.
+template <int NT = 1024>
 struct TableRegs {
-  uint32_t a64, fold[kFoldTabs];
+  static_assert(1024 % NT == 0, "every thread stages the same number of entries");
+  static constexpr int kPer = 1024 / NT;
+  uint32_t a64[kPer], fold[kFoldTabs][kPer];
 };
-__device__ __forceinline__ TableRegs table_loads(const uint32_t* tabs) {
-  TableRegs r;
-  r.a64 = tabs[threadIdx.x];
+template <int NT = 1024>
+__device__ __forceinline__ TableRegs<NT> table_loads(const uint32_t* tabs) {
+  TableRegs<NT> r;
 #pragma unroll
-  for (int k = 0; k < kFoldTabs; k++) r.fold[k] = tabs[1024 + k * 1024 + threadIdx.x];
+  for (int i = 0; i < r.kPer; i++) {
+    const uint32_t e = threadIdx.x + (uint32_t)(i * NT);
+    r.a64[i] = tabs[e];
+#pragma unroll
+    for (int k = 0; k < kFoldTabs; k++) r.fold[k][i] = tabs[1024 + k * 1024 + e];
+  }
   return r;
 }
-__device__ __forceinline__ void table_writes(uint32_t* lds, const TableRegs& r) {
+template <int NT>
+__device__ __forceinline__ void table_writes(uint32_t* lds, const TableRegs<NT>& r) {
   typedef __attribute__((address_space(3))) u32x4_t lds_u32x4_t;
-  const uint32_t e = threadIdx.x;
-  const uint32_t k = e >> 8, val = e & 255u;
-  const u32x4_t s = {r.a64, r.a64, r.a64, r.a64};
-  lds_u32x4_t* dst = (lds_u32x4_t*)((k >> 1) * 65536u + val * 256u + (k & 1u) * 128u);
-#pragma unroll
-  for (int c = 0; c < kRep / 4; c++) dst[c] = s;
   uint32_t* fold = lds + kRepDwords;
 #pragma unroll
-  for (int k2 = 0; k2 < kFoldTabs; k2++) fold[k2 * 1024 + e] = r.fold[k2];
+  for (int i = 0; i < r.kPer; i++) {
+    const uint32_t e = threadIdx.x + (uint32_t)(i * NT);
+    const uint32_t k = e >> 8, val = e & 255u;
+    const u32x4_t s = {r.a64[i], r.a64[i], r.a64[i], r.a64[i]};
+    lds_u32x4_t* dst = (lds_u32x4_t*)((k >> 1) * 65536u + val * 256u + (k & 1u) * 128u);
+#pragma unroll
+    for (int c = 0; c < kRep / 4; c++) dst[c] = s;
+#pragma unroll
+    for (int k2 = 0; k2 < kFoldTabs; k2++) fold[k2 * 1024 + e] = r.fold[k2][i];
+  }
 }
 __device__ __forceinline__ void stage_tables(uint32_t* lds, const uint32_t* tabs) {
   table_writes(lds, table_loads(tabs));
@@ -1111,7 +1124,7 @@ unpack_fixed_kernel(UnpackParams p, uint32_t expect) {
   uint32_t* rep = lds;
   uint32_t* fold = lds + kRepDwords;  // [A4 | A8 | A12 | A16 | A32 | A48]
   const uint8_t* ldsb = reinterpret_cast<const uint8_t*>(rep);
-  const TableRegs tab_regs = table_loads(p.tabs);  // staged below, after the first rows
+  const TableRegs<> tab_regs = table_loads(p.tabs);  // staged below, after the first rows
   asm volatile("" ::: "memory");  // these loads issue before the rows (in-order vmcnt)
 
   const int lane = threadIdx.x & 63;
@@ -1466,24 +1479,36 @@ unpack_fixed_kernel(UnpackParams p, uint32_t expect) {
 // the rows of its last K = 16 groups in registers (2 dwords per group and lane, written by a
 // wave-uniform indexed move) and stores them in one burst every K groups and at its end: for
 // config 2 (16 groups per wave) one burst, after the wave's reads (measured 0.194 ms against
-// 0.215 ms for the interleaved kernel on the same box; K = 12 with two bursts: 0.204 ms).  The
-// registers come from a shorter load ring: RS = 4 rows per wave (4 KiB per wave, 64 KiB per
-// CU), reloaded as a BLOCK: when the last of the RS rows is consumed, rows r + 4 .. r + 7 of
-// the wave's row stream are requested by four back-to-back loads.  Rows 2j and 2j + 1 are the
-// halves of a record's 128-byte line, and a block is two whole lines per record; requesting
-// them together measured 4% faster than one reload per consumed row (0.187 against 0.195 ms,
-// DESIGN 4.1), although the wave then computes with nothing of its own in flight.
+// 0.215 ms for the interleaved kernel on the same box; K = 12 with two bursts: 0.204 ms).
+// The load ring is NB blocks of BR rows per wave, each reloaded as a BLOCK: when the last of a
+// block's rows is consumed, the rows RS = NB * BR further on in the wave's row stream are
+// requested by BR back-to-back loads.  Rows 2j and 2j + 1 are the halves of a record's 128-byte
+// line; requesting whole lines together measured 4% faster than one reload per consumed row.
+// The product shape is ONE block of 4 rows (two lines per record, 4 KiB per wave, 0 .. 64 KiB
+// in flight per CU) at 16 waves per workgroup, K = 16: the wave computes with nothing of its
+// own in flight and the CU's other waves cover it.  Every shape that keeps more in flight --
+// a second block (16 or 8 waves per workgroup, K = 32 at 8), or one block of 8 rows at 16
+// waves -- measured 6-7% SLOWER on config 2 (0.199 against 0.186 ms, DESIGN 4.1 "r08"; the
+// shapes stay in the diagnostics build, launch_unpack variants 17..32).  What did pay there
+// is the kind of load: the loads that open a group in the ring are non-temporal (kNt), the
+// reloads inside the group plain: 0.1744 against 0.1873 ms.
+// A ring of two records' rows (512-byte records with RS = 16, diagnostics only) runs two
+// groups per loop trip so that every ring index stays static.
 // Semantics are those of unpack_fixed_kernel<NR, 0, true, true>.
-template <int NR, int RS = 4, int K = 16>
-__global__ void __launch_bounds__(kUnpackThreads)
+template <int NR, int BR = 4, int NB = 1, int K = 16, int NW = 16, bool kNt = false>
+__global__ void __launch_bounds__(NW * 64)
 unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
+  // BR: rows per load block; NB: blocks in a wave's ring; K: groups of row output held per
+  // wave before a burst; NW: waves per workgroup
+  constexpr int RS = NB * BR;               // rows in the ring
+  constexpr int G = RS > NR ? RS / NR : 1;  // groups the ring holds rows of
   static_assert(NR == 8 || NR == 16, "ring kernel: 512- or 1024-byte records");
-  static_assert(NR % RS == 0, "the ring divides the record's rows");
-  // RS: rows per load block of a wave; K: groups of row output held per wave before a burst
+  static_assert(NR % BR == 0, "a block lies inside one record");
+  static_assert(RS <= NR ? NR % RS == 0 : (RS == 2 * NR && BR == NR), "static ring indices");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t* fold = lds + kRepDwords;  // [A4 | A8 | A12 | A16 | A32 | A48]
   const uint8_t* ldsb = reinterpret_cast<const uint8_t*>(lds);
-  const TableRegs tab_regs = table_loads(p.tabs);
+  const TableRegs<NW * 64> tab_regs = table_loads<NW * 64>(p.tabs);
   asm volatile("" ::: "memory");
 
   const int lane = threadIdx.x & 63;
@@ -1510,7 +1535,13 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
   // quad lane q keeps dwords 2q, 2q + 1 of the record's row: lane masks, not branches
   const uint32_t qm0 = 0u - (uint32_t)(q == 0), qm1 = 0u - (uint32_t)(q == 1);
   const uint32_t qm2 = 0u - (uint32_t)(q == 2), qm3 = 0u - (uint32_t)(q == 3);
-  auto ld = [&](uint32_t base, int j) { return ldu128(p.slab + (uint64_t)base + 64 * j); };
+  // the loads that bring a group into the ring (the prime, and the reloads with rows of a later
+  // group); kNt: non-temporal.  Reloads with later rows of the group being folded (a ring
+  // shorter than a record) are always plain loads -- that mix is what was measured, DESIGN 4.1
+  auto ld = [&](uint32_t base, int j) {
+    const uint8_t* a = p.slab + (uint64_t)base + 64 * j;
+    return kNt ? ldnt128(a) : ldu128(a);
+  };
   auto decide = [&](const u32x4_t& pf, bool live) {
     const uint32_t w0 = prefix_word(pf, 0);
     const uint32_t w5 = prefix_word(pf, 5);
@@ -1606,68 +1637,94 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
   };
 
   u32x4_t d[RS];
+  // The ring holds rows of G consecutive groups of the wave: slot s (ring rows s * NR ..) those
+  // of group g + s * n_waves.  idxq / liveq: record index and liveness of those groups' lanes;
+  // base: the row base of group g (only a ring shorter than a record reads more of group g).
   uint32_t g = wave_id;
-  uint32_t idx = rec_idx(g < g_end ? g : 0u);
-  bool live = is_live(idx);
-  uint32_t base = row_base(idx, live);
+  uint32_t idxq[G];
+  bool liveq[G];
+  uint32_t base = 0;
+  // the whole ring, from group g on (a group past the wave's last: group g's rows again)
+  auto prime = [&]() {
+    const uint32_t g0 = g < g_end ? g : 0u;
 #pragma unroll
-  for (int j = 0; j < RS; j++) {
-    d[j] = ld(base, j);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+    for (int s = 0; s < G; s++) {
+      const uint32_t gs = g + (uint32_t)s * n_waves;
+      idxq[s] = rec_idx(gs < g_end ? gs : g0);
+      liveq[s] = is_live(idxq[s]);
+      const uint32_t b = row_base(idxq[s], liveq[s]);
+      if (s == 0) base = b;
+#pragma unroll
+      for (int j = 0; j < (RS < NR ? RS : NR); j++) {
+        d[s * NR + j] = ld(b, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+  prime();
   table_writes(lds, tab_regs);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (g >= g_end) return;
 
-  // Two modes, each in its own loop.  The pipelined loop is the only place that redefines
-  // the ring inside a loop, and it does so in place (slot t % RS by row t + RS of the wave's
-  // row stream); the header-only loop never touches the ring, and the switch back re-primes
-  // it outside both.  (In one mixed loop the header-only path's second definition of the
-  // ring made LLVM copy the whole ring at the back edge, 16 moves per group.)
-  for (;;) {
-    // ---- pipelined groups: d[] holds rows 0 .. RS-1 of group g; idx, live, base are g's
-    bool more;
-    do {
-      const uint32_t gn = g + n_waves;
-      const bool has_next = gn < g_end;
-      const uint32_t idx_n = rec_idx(has_next ? gn : g);
-      const bool live_n = is_live(idx_n);
-      const uint32_t base_n = row_base(idx_n, live_n);
-      const u32x4_t hdr = d[0];  // row 0 = the 64-byte header prefix (aligned)
-      const bool needs_crc = decide(hdr, live);
-      const bool any = __any(needs_crc);
-      uint32_t o0, o1;
+  // One pipelined group: group g, whose rows sit in slot S of the ring.  When the last row of
+  // a block has been read out of the ring, the block's BR registers are reloaded in place, back
+  // to back, with the rows RS further on in the wave's row stream: later rows of group g (a
+  // ring shorter than a record), or the same block of group g + G * n_waves.  So NB - 1 blocks
+  // are in flight while one is folded.  Returns whether the wave's next group is pipelined too.
+  // `run` (wave-uniform; constant true unless G = 2) = false: there is no such group, and the
+  // step only requests the slot's last block again, so that the loads in flight are in the
+  // same order on every path through the loop (the compiler's waits count on that order).
+  auto step = [&](auto slot_c, bool run) -> bool {
+    constexpr int S = decltype(slot_c)::value;
+    constexpr auto ri = [](int j) { return (S * NR + j) % RS; };  // ring index of g's row j
+    const uint32_t idx = idxq[0];
+    const bool live = liveq[0];
+    const bool has_next = g + n_waves < g_end;
+    const uint32_t gn = g + (uint32_t)G * n_waves;  // the group whose rows are requested here
+    const uint32_t idx_n = rec_idx(gn < g_end ? gn : g);
+    const bool live_n = is_live(idx_n);
+    const uint32_t base_n = row_base(idx_n, live_n);
+    bool needs_crc = false, any = false;
+    uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u, f2 = 0u, f3 = 0u;
+    if (run) {
+      const u32x4_t hdr = d[ri(0)];  // row 0 = the 64-byte header prefix (aligned)
+      needs_crc = decide(hdr, live);
+      any = __any(needs_crc);
       decode(hdr, idx, live, o0, o1);
       uint32_t ha[4] = {0u, 0u, 0u, 0u}, hb[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
       for (int j = 0; j < NR - 1; j++) {
-        const u32x4_t x = d[j % RS];
+        const u32x4_t x = d[ri(j)];
         const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
         uint32_t c4[4];
 #pragma unroll
         for (int b = 0; b < 4; b++) c4[b] = xor3(ha[b], hb[b], xw[b]);
         __builtin_amdgcn_sched_barrier(0);
-        // the block's last row is out of the ring: the next block of the stream (this group's
-        // rows, or the next group's first RS), back to back
-        if ((j % RS) == RS - 1) {
+        // the block's last row is out of the ring: reload the block
+        if ((j % BR) == BR - 1) {
 #pragma unroll
-          for (int t = j - (RS - 1); t <= j; t++)
-            d[t % RS] = (t + RS < NR) ? ld(base, t + RS) : ld(base_n, t + RS - NR);
+          for (int t = j - (BR - 1); t <= j; t++) {
+            if (t + RS < NR) d[ri(t)] = ldu128(p.slab + (uint64_t)base + 64 * (t + RS));
+            else d[ri(t)] = ld(base_n, (t + RS) % NR);
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 4; b++) a64_parts(ldsb, c4[b], s1, ha[b], hb[b]);
       }
-      const u32x4_t xf = d[(NR - 1) % RS];
-      uint32_t f0 = xor3(ha[0], hb[0], xf.x), f1 = xor3(ha[1], hb[1], xf.y);
-      uint32_t f2 = xor3(ha[2], hb[2], xf.z);
-      uint32_t f3 = xor3(ha[3], hb[3], q == 3 ? bswap32(xf.w) : xf.w);
-      asm volatile("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3));
-      __builtin_amdgcn_sched_barrier(0);
+      const u32x4_t xf = d[ri(NR - 1)];
+      f0 = xor3(ha[0], hb[0], xf.x);
+      f1 = xor3(ha[1], hb[1], xf.y);
+      f2 = xor3(ha[2], hb[2], xf.z);
+      f3 = xor3(ha[3], hb[3], q == 3 ? bswap32(xf.w) : xf.w);
+    }
+    asm volatile("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3));
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int t = NR - RS; t < NR; t++) d[t % RS] = ld(base_n, t + RS - NR);
-      __builtin_amdgcn_sched_barrier(0);
+    for (int t = NR - BR; t < NR; t++) d[ri(t)] = ld(base_n, (t + RS) % NR);
+    __builtin_amdgcn_sched_barrier(0);
+    if (run) {
       const uint32_t v = shift_tab(fold + 3 * 1024, f0) ^ shift_tab(fold + 2 * 1024, f1) ^
                          shift_tab(fold + 1 * 1024, f2) ^ shift_tab(fold, f3);
       const uint32_t* lt = fold + (q == 0 ? 5 : (q == 1 ? 4 : 3)) * 1024;  // A48/A32/A16
@@ -1677,29 +1734,58 @@ unpack_fixed_ring_kernel(UnpackParams p, uint32_t expect) {
       verdict(o0, needs_crc && sum != expect);
       push(o0, o1, g);
       if (held == (uint32_t)K) flush();
-      g = gn;
-      idx = idx_n;
-      live = live_n;
-      base = base_n;
-      // a group without checksummed records: its successors run header-only (the rows of
-      // the next group in flight are simply overwritten later)
-      more = has_next && any;
-    } while (more);
+      g += n_waves;
+#pragma unroll
+      for (int s = 0; s + 1 < G; s++) {
+        idxq[s] = idxq[s + 1];
+        liveq[s] = liveq[s + 1];
+      }
+      idxq[G - 1] = idx_n;
+      liveq[G - 1] = live_n;
+      if (G == 1) base = base_n;
+    }
+    // a group without checksummed records: its successors run header-only (the rows of
+    // the following groups in flight are simply overwritten later)
+    return run && has_next && any;
+  };
+
+  // Two modes, each in its own loop.  The pipelined loop is the only place that redefines
+  // the ring inside a loop, and it does so in place; G groups per trip, so that every ring
+  // index is static.  The header-only loop never touches the ring, and the switch back
+  // re-primes the whole of it outside both.  (In one mixed loop the header-only path's second
+  // definition of the ring made LLVM copy the whole ring at the back edge.)
+  for (;;) {
+    // ---- pipelined groups: slot 0 of the ring holds the rows of group g
+    if (G == 1) {
+      while (step(std::integral_constant<int, 0>{}, true)) {
+      }
+    } else {
+      // Two groups per trip, and no way out of the loop between them: the compiler
+      // structurizes this loop (its body has divergent branches), which turns an exit after the
+      // first step into a path around the second one to the back edge.  Along that path the
+      // first slot's reloads would be the youngest loads, and every wait of the first step
+      // would become a drain of both blocks (seen in the assembly: vmcnt(7) .. (0)).
+      bool more;
+      do {
+        const bool two = step(std::integral_constant<int, 0>{}, true);
+        more = step(std::integral_constant<int, G - 1>{}, two);
+      } while (more);
+    }
     // ---- header-only groups: header first, body only when a record needs the CRC
     for (; g < g_end; g += n_waves) {
-      idx = rec_idx(g);
-      live = is_live(idx);
-      base = row_base(idx, live);
-      const u32x4_t ph = ld(base, 0);
-      if (__any(decide(ph, live))) break;
+      const uint32_t i = rec_idx(g);
+      const bool lv = is_live(i);
+      // (a plain load: the line is read again if the group turns out to need the CRC)
+      const u32x4_t ph = ldu128(p.slab + (uint64_t)row_base(i, lv));
+      if (__any(decide(ph, lv))) break;
       uint32_t o0, o1;
-      decode(ph, idx, live, o0, o1);
+      decode(ph, i, lv, o0, o1);
       push(o0, o1, g);
       if (held == (uint32_t)K) flush();
     }
     if (g >= g_end) break;
-    // ---- back to the pipelined mode at group g: its first RS rows
-    for (int j = 0; j < RS; j++) d[j] = ld(base, j);
+    // ---- back to the pipelined mode at group g
+    prime();
   }
   if (held) flush();
 }
@@ -2007,14 +2093,29 @@ static hipError_t launch_fixed(const UnpackParams& p, int grid, hipStream_t stre
   return hipGetLastError();
 }
 
-template <int NR, int RS = 4, int K = 16>
-static hipError_t launch_ring(const UnpackParams& p, int grid, hipStream_t stream) {
-  hipError_t e = set_max_lds((const void*)unpack_fixed_ring_kernel<NR, RS, K>, (int)kUnpackLdsBytes);
+// The ring kernel sizes its own grid: one workgroup of NW waves per CU, a group per wave at
+// least -- min(ceil(groups / NW), CUs).
+template <int NR, int BR = 4, int NB = 1, int K = 16, int NW = 16, bool kNt = false>
+static hipError_t launch_ring(const UnpackParams& p, int cus, hipStream_t stream) {
+  const auto kernel = unpack_fixed_ring_kernel<NR, BR, NB, K, NW, kNt>;
+  hipError_t e = set_max_lds((const void*)kernel, (int)kUnpackLdsBytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((unpack_fixed_ring_kernel<NR, RS, K>), dim3(grid), dim3(kUnpackThreads),
-                     kUnpackLdsBytes, stream, p, p.expect_fixed);
+  const uint64_t groups = ((uint64_t)p.n + 15) / 16;
+  uint64_t grid = (groups + NW - 1) / NW;
+  if (grid > (uint64_t)cus) grid = (uint64_t)cus;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NW * 64), kUnpackLdsBytes, stream, p,
+                     p.expect_fixed);
   return hipGetLastError();
 }
+
+// Non-temporal ring loads, by batch size (scripts/ring_shapes.py, plain against non-temporal,
+// us per launch on one MI355X, the same slab read again by every launch):
+//   1024-B records   65,536: 16.9 / 16.5   131,072: 27.0 / 26.3   1,048,576: 185.5 / 172.6
+//    512-B records  131,072: 15.6 / 16.2   262,144: 26.1 / 26.9   393,216: 36.5 / 36.4
+//                   524,288: 47.2 / 46.1   1,048,576: 97.5 / 85.3
+// So 1024-byte records always load non-temporally, 512-byte records from 393,216 records
+// (24,576 groups) up.
+constexpr uint32_t kRingNt512Groups = 24576;
 
 typedef hipError_t (*fixed_launcher)(const UnpackParams&, int, hipStream_t);
 #define MGENX_FIXED_TABLE(R)                                                              \
@@ -2027,7 +2128,8 @@ static const fixed_launcher kFixedLaunch[17] = MGENX_FIXED_TABLE(false);
 static const fixed_launcher kFixedLaunchRows[17] = MGENX_FIXED_TABLE(true);
 #undef MGENX_FIXED_TABLE
 
-hipError_t launch_unpack(const UnpackParams& p, int grid, hipStream_t stream, int* which) {
+hipError_t launch_unpack(const UnpackParams& p, int grid, int cus, hipStream_t stream,
+                         int* which) {
   const int unpack_variant = p.variant;
   *which = MGENX_UNPACK_K_OTHER;
   if (p.opts & MGENX_OPT_SKIP_CRC) {
@@ -2051,9 +2153,12 @@ hipError_t launch_unpack(const UnpackParams& p, int grid, hipStream_t stream, in
     switch (p.fixed_len) {
       case 256: return c.rows ? launch_fixed<4, 0, true, true>(p, grid, stream)
                               : launch_fixed<4, 0, false, true>(p, grid, stream);
-      case 512: return c.rows ? launch_ring<8>(p, grid, stream)
-                              : launch_fixed<8, 0, false, true>(p, grid, stream);
-      case 1024: return c.rows ? launch_ring<16>(p, grid, stream)
+      case 512:
+        if (!c.rows) return launch_fixed<8, 0, false, true>(p, grid, stream);
+        return (p.n + 15u) / 16u >= kRingNt512Groups
+                   ? launch_ring<8, 4, 1, 16, 16, true>(p, cus, stream)
+                   : launch_ring<8, 4, 1, 16, 16, false>(p, cus, stream);
+      case 1024: return c.rows ? launch_ring<16, 4, 1, 16, 16, true>(p, cus, stream)
                                : launch_fixed<16, 0, false, true>(p, grid, stream);
       default: break;
     }
@@ -2066,9 +2171,76 @@ hipError_t launch_unpack(const UnpackParams& p, int grid, hipStream_t stream, in
                   : launch_fixed<16, 0, false, true>(p, grid, stream);
   // ring-kernel shapes (rows in flight, groups held): 14 = (8, 12), 15 = (8, 8), 16 = (4, 12)
   if (unpack_variant >= 14 && unpack_variant <= 16 && fixed && p.fixed_len == 1024 && c.rows) {
-    if (unpack_variant == 14) return launch_ring<16, 8, 12>(p, grid, stream);
-    if (unpack_variant == 15) return launch_ring<16, 8, 8>(p, grid, stream);
-    return launch_ring<16, 4, 12>(p, grid, stream);
+    if (unpack_variant == 14) return launch_ring<16, 8, 1, 12>(p, cus, stream);
+    if (unpack_variant == 15) return launch_ring<16, 8, 1, 8>(p, cus, stream);
+    return launch_ring<16, 4, 1, 12>(p, cus, stream);
+  }
+  // ring-kernel shapes (waves, block rows, blocks, groups held): 17 = (16, 4, 1, 16),
+  // 18 = (8, 8, 2, 32), 19 = (8, 4, 4, 32; 1024-byte records only)
+  if (unpack_variant >= 17 && unpack_variant <= 19 && fixed && c.rows &&
+      (p.fixed_len == 1024 || (p.fixed_len == 512 && unpack_variant != 19))) {
+    *which = MGENX_UNPACK_K_FIXED_RING;
+    const bool r16 = p.fixed_len == 1024;
+    if (unpack_variant == 17)
+      return r16 ? launch_ring<16, 4, 1, 16, 16>(p, cus, stream)
+                 : launch_ring<8, 4, 1, 16, 16>(p, cus, stream);
+    if (unpack_variant == 18)
+      return r16 ? launch_ring<16, 8, 2, 32, 8>(p, cus, stream)
+                 : launch_ring<8, 8, 2, 32, 8>(p, cus, stream);
+    return launch_ring<16, 4, 4, 32, 8>(p, cus, stream);
+  }
+  // 16-wave shapes with a second block in the ring: 20 = (16, 4, 2, 16), 21 = (16, 2, 4, 16),
+  // 22 = (16, 2, 2, 16)
+  if (unpack_variant >= 20 && unpack_variant <= 22 && fixed && c.rows && !p.rec_len &&
+      (p.fixed_len == 512 || p.fixed_len == 1024)) {
+    *which = MGENX_UNPACK_K_FIXED_RING;
+    const bool r16 = p.fixed_len == 1024;
+    if (unpack_variant == 20)
+      return r16 ? launch_ring<16, 4, 2, 16, 16>(p, cus, stream)
+                 : launch_ring<8, 4, 2, 16, 16>(p, cus, stream);
+    if (unpack_variant == 21)
+      return r16 ? launch_ring<16, 2, 4, 16, 16>(p, cus, stream)
+                 : launch_ring<8, 2, 4, 16, 16>(p, cus, stream);
+    return r16 ? launch_ring<16, 2, 2, 16, 16>(p, cus, stream)
+               : launch_ring<8, 2, 2, 16, 16>(p, cus, stream);
+  }
+  // non-temporal row loads: 27 = (8, 8, 2, 32), 28 = (16, 4, 1, 16), 29 = (16, 4, 2, 16),
+  // 30 = (16, 2, 1, 16), 31 = (8, 8, 1, 32), 32 = (16, 8, 1, 16)
+  if (unpack_variant >= 27 && unpack_variant <= 32 && fixed && c.rows && !p.rec_len &&
+      (p.fixed_len == 512 || p.fixed_len == 1024)) {
+    *which = MGENX_UNPACK_K_FIXED_RING;
+    const bool r16 = p.fixed_len == 1024;
+    switch (unpack_variant) {
+      case 27: return r16 ? launch_ring<16, 8, 2, 32, 8, true>(p, cus, stream)
+                          : launch_ring<8, 8, 2, 32, 8, true>(p, cus, stream);
+      case 28: return r16 ? launch_ring<16, 4, 1, 16, 16, true>(p, cus, stream)
+                          : launch_ring<8, 4, 1, 16, 16, true>(p, cus, stream);
+      case 29: return r16 ? launch_ring<16, 4, 2, 16, 16, true>(p, cus, stream)
+                          : launch_ring<8, 4, 2, 16, 16, true>(p, cus, stream);
+      case 30: return r16 ? launch_ring<16, 2, 1, 16, 16, true>(p, cus, stream)
+                          : launch_ring<8, 2, 1, 16, 16, true>(p, cus, stream);
+      case 31: return r16 ? launch_ring<16, 8, 1, 32, 8, true>(p, cus, stream)
+                          : launch_ring<8, 8, 1, 32, 8, true>(p, cus, stream);
+      default: return r16 ? launch_ring<16, 8, 1, 16, 16, true>(p, cus, stream)
+                          : launch_ring<8, 8, 1, 16, 16, true>(p, cus, stream);
+    }
+  }
+  // one block of another size: 23 = (16, 8, 1, 16), 24 = (16, 2, 1, 16), 25 = (8, 8, 1, 32),
+  // 26 = (8, 16, 1, 32; 1024-byte records only)
+  if (unpack_variant >= 23 && unpack_variant <= 26 && fixed && c.rows && !p.rec_len &&
+      (p.fixed_len == 1024 || (p.fixed_len == 512 && unpack_variant != 26))) {
+    *which = MGENX_UNPACK_K_FIXED_RING;
+    const bool r16 = p.fixed_len == 1024;
+    if (unpack_variant == 23)
+      return r16 ? launch_ring<16, 8, 1, 16, 16>(p, cus, stream)
+                 : launch_ring<8, 8, 1, 16, 16>(p, cus, stream);
+    if (unpack_variant == 24)
+      return r16 ? launch_ring<16, 2, 1, 16, 16>(p, cus, stream)
+                 : launch_ring<8, 2, 1, 16, 16>(p, cus, stream);
+    if (unpack_variant == 25)
+      return r16 ? launch_ring<16, 8, 1, 32, 8>(p, cus, stream)
+                 : launch_ring<8, 8, 1, 32, 8>(p, cus, stream);
+    return launch_ring<16, 16, 1, 32, 8>(p, cus, stream);
   }
   // ablation 12: the unaligned (separate header load) path on 1024-B records
   if (unpack_variant == 12 && fixed && p.fixed_len == 1024)
