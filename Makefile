@@ -5,10 +5,12 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value -Wno-int-to-pointer-cast
-NAMES := mgenx_api mgenx_unpack mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_comm mgenx_worker \
+NAMES := mgenx_api mgenx_unpack mgenx_unpack_fixed mgenx_probe \
+         mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_comm mgenx_worker \
          mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse mgenx_flowdist mgenx_defrag
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
-       mgen_amd/csrc/mgenx_flowsm.hpp \
+       mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
+       mgen_amd/csrc/mgenx_unpack_long.hpp mgen_amd/csrc/mgenx_flowsm.hpp \
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \
        mgen_amd/csrc/mgenx_flowdist.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))

@@ -15,17 +15,13 @@ extern "C" {
 #endif
 
 /* Tuning knobs (per context; for benchmarking kernel variants).  MGENX_TUNE_UNPACK_VARIANT:
- * 0 = automatic (pipelined fixed-length kernel when the batch qualifies), 1/2 = ablations
- * of the general kernel (loads+XOR only / lookups on cached rows), 3 = general kernel,
- * 12 = fixed-length kernel with a separate header load (1024-B records), 1024 + M =
- * ablation bit mask M of the aligned 1024-B kernel (1 = no LDS lookups, 2 = no decode and
- * no stores, 4 = decode without stores, 8 = stores to a scratch line, 16 = the other store
- * cache policy, 32 = stores wrapped onto the first 16K records, 64 = write-through stores,
- * 128 = non-temporal row loads, 256 (with 4) = dummy rows stored after each wave's last
- * group), 40-45 = long-record kernel shapes (rows per block x threads: 16x512, 8x512,
- * 4x1024, 12x512, 2x1024, 16x1024), 17-32 = ring-kernel shapes on fixed 512/1024-B records
- * with row output (waves per workgroup, rows per block, blocks, groups held; 27-32 with
- * non-temporal loads: the table in launch_unpack, timed by scripts/ring_shapes.py). */
+ * 0 = the product dispatch.  The other values are listed in one table, kUnpackVariants in
+ * mgen_amd/csrc/mgenx_unpack.hip, each with the kind of batch it applies to and a
+ * description.  They are of three kinds: ablations of a product kernel (what bounds it: loads
+ * only, no tail, no stores, stores to a scratch line, the other cache policy), a product
+ * kernel forced onto a batch the dispatch would route elsewhere, and the few shapes a
+ * committed test or script still runs.  A variant that does not apply to the batch (or a
+ * number not in the table) leaves the batch to the long / var / general kernels. */
 #define MGENX_TUNE_UNPACK_VARIANT 1
 /* MGENX_TUNE_PACK_VARIANT: 0 = product; ablations 1 = no unit stores, 2 = no CRC work, 3-6
  * store-scheme ablations, 7-9 = grid x2..x4, 10 = the meta waves never help the joint

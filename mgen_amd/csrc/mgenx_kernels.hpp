@@ -98,8 +98,7 @@ struct PackParams {
 // the ring kernel (its own wave count per workgroup) sizes its grid from `cus` by the same rule
 hipError_t launch_unpack(const UnpackParams& p, int grid, int cus, hipStream_t stream,
                          int* which);
-// tuning knob (mgenx_set_tuning): 0 = auto (pipelined fixed-length kernel when the batch
-// qualifies), 1/2 = ablations of the general kernel, 3 = general kernel only
+// (UnpackParams::variant, diagnostics build: the table kUnpackVariants in mgenx_unpack.hip)
 int unpack_threads();
 #if MGENX_DIAG
 hipError_t launch_group_rw(const uint8_t* p, uint64_t bytes, uint8_t* out, int mode, int grid,

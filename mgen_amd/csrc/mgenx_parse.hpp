@@ -1,5 +1,5 @@
 // mgenx_parse.hpp -- MgenMsg::Unpack of one record by one lane (mgenMsg.cpp:315-500): the
-// general-layout path of the batch kernels (mgenx_unpack.hip) and the resident single-message
+// general-layout path of the batch kernels (mgenx_unpack*.hip) and the resident single-message
 // worker (mgenx_worker.hip).
 #pragma once
 

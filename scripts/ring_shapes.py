@@ -1,7 +1,8 @@
 """Config 2 unpack (fixed 512- and 1024-byte records, checksummed, 32-B rows) through the
-ring-kernel shapes of the diagnostics build (MGENX_TUNE_UNPACK_VARIANT 17..32, see
+ring-kernel shapes of the diagnostics build (MGENX_TUNE_UNPACK_VARIANT, the table in
 launch_unpack): waves per workgroup, rows per load block, blocks in the ring, groups of row
-output held, and plain or non-temporal row loads.  Batches of 65,536, 131,072 (the pcie_inclusive_config2 chunk) and 1,048,576
+output held, and plain or non-temporal row loads.  The shapes that lost were retired with
+their numbers on record (profiles/r08/ring_shapes.txt).  Batches of 65,536, 131,072 (the pcie_inclusive_config2 chunk) and 1,048,576
 records.  Every shape's rows are compared with the product kernel's (bit-exact) before timing;
 the slab carries bit flips, so the CRC verdicts are part of the comparison."""
 import os
@@ -14,13 +15,8 @@ from mgen_amd import PACK_CHECKSUM, Engine, to_device  # noqa: E402
 from mgen_amd.workloads import udp_fixed  # noqa: E402
 
 N = 1 << 20
-SHAPES = {0: "product", 17: "(16, 4, 1, 16)", 18: "(8, 8, 2, 32)", 19: "(8, 4, 4, 32)",
-          20: "(16, 4, 2, 16)", 21: "(16, 2, 4, 16)", 22: "(16, 2, 2, 16)",
-          23: "(16, 8, 1, 16)", 24: "(16, 2, 1, 16)", 25: "(8, 8, 1, 32)", 26: "(8, 16, 1, 32)",
-          27: "(8, 8, 2, 32) nt", 28: "(16, 4, 1, 16) nt", 29: "(16, 4, 2, 16) nt",
-          30: "(16, 2, 1, 16) nt", 31: "(8, 8, 1, 32) nt", 32: "(16, 8, 1, 16) nt"}
-VARIANTS = [int(v) for v in os.environ.get(
-    "VARIANTS", "17,18,19,20,21,22,23,24,25,26,27,28,29,30,31,32,0").split(",")]
+SHAPES = {0: "product", 17: "(16, 4, 1, 16)", 18: "(8, 8, 2, 32)", 28: "(16, 4, 1, 16) nt"}
+VARIANTS = [int(v) for v in os.environ.get("VARIANTS", "17,18,28,0").split(",")]
 BATCHES = [int(v) for v in os.environ.get("BATCHES", "65536,131072,1048576").split(",")]
 eng = Engine(0, diag=True)
 rows = {"rows": eng.alloc_rows(N)}
@@ -47,7 +43,7 @@ for L in (1024, 512):
     # a bit flip in every 1000th record, at a position that walks through the record
     recs = torch.arange(0, N, 1000, device="cuda", dtype=torch.int64)
     slab[recs * L + (recs * 7) % L] ^= 0x10
-    variants = [v for v in VARIANTS if not (L == 512 and v in (19, 26))]
+    variants = VARIANTS
     for n in BATCHES:
         def run():
             eng.unpack(slab, n, stride=L, fixed_len=L, cols=rows)

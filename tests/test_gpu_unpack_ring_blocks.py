@@ -2,7 +2,10 @@
 own: the product shape (16 waves per workgroup, one 4-row block, 16 groups of row output held,
 non-temporal row loads) and the diagnostics build's two-block shape 18 (8 waves, two 8-row
 blocks, 32 groups held), whose 512-byte form keeps two groups in the ring and runs two groups
-per loop trip.  SHAPES is the one place that states each shape's wave count and K; every size
+per loop trip.  Variants 17 and 28 are the product shape with plain and with non-temporal loads
+whatever the batch size (the dispatch picks plain loads for 512-byte batches under 393,216
+records and never for 1024-byte ones, so every case here also runs the instantiations the
+product reaches only at other sizes).  SHAPES is the one place that states each shape's wave count and K; every size
 below is derived from it, so that the cases land on the edges of W = waves x CUs: trip counts
 1, 2, 3 (odd and even) with a partial last group, waves without a group, bit flips on both
 sides of the block seam and in the first rows of each reloaded block, every order of
@@ -24,8 +27,8 @@ pytestmark = pytest.mark.gpu
 CORE = COLMAP[:13]
 # unpack variant of the diagnostics build (0 = the product library's dispatch) ->
 # (waves per workgroup, K = groups of row output held per wave); see launch_unpack
-SHAPES = {0: (16, 16), 18: (8, 32)}
-SHAPE_IDS = {0: "product", 18: "two_blocks"}
+SHAPES = {0: (16, 16), 18: (8, 32), 17: (16, 16), 28: (16, 16)}
+SHAPE_IDS = {0: "product", 18: "two_blocks", 17: "plain_loads", 28: "nt_loads"}
 
 
 @pytest.fixture(scope="module")
