@@ -1015,6 +1015,130 @@ int mgenx_pcapng_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
                         uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
                         mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream);
 
+/* ---- pcap2mgen: MGEN messages sent over TCP (an option; the reference drops every packet that
+ * is not UDP, pcap2mgen.cpp:425, and without these calls nothing below happens) ----
+ * mgenx_pcap_tcp / mgenx_pcapng_tcp run after the parse, the snap step and the defrag step,
+ * over the same packets: captured segments -> each connection's byte stream, in scratch.
+ *
+ * Which packets are segments.
+ *   Every packet whose status is not OOB is examined.  The walk is the parse's link / IP walk,
+ *   but without the 4094-byte frame rule (num = caplen): a capture taken on the sending host
+ *   holds segments of up to 64 KiB before segmentation offload.
+ *   - IPv4: ihl >= 20, tot >= ihl, ip0 + tot <= wire length (SLL: the captured length, as the
+ *     parse), not a fragment (MF == 0 and off == 0), protocol 6.
+ *   - IPv6: the fixed header's next header is 6.  No extension headers are opened.
+ *   - l4 is the IP payload start and ip_end = ip0 + tot (v6: ip0 + 40 + pl).  Ethernet padding
+ *     past ip_end is not payload.
+ *   - The 20 TCP header bytes must lie inside num and inside ip_end.
+ *     doff = (b[l4+12] >> 4) * 4 must be >= 20, and l4 + doff <= ip_end.
+ *   - Anything else is not a segment and stays untouched.
+ *   - A segment whose payload [l4+doff, ip_end) is not wholly inside num (ip_end > num) gets
+ *     MGENX_PCAP_TRUNCATED and takes no part.
+ *   - Every other segment gets MGENX_PCAP_TCP.  udp_len, udp_off and src keep what the parse
+ *     wrote.
+ *   - Key: (version, src addr, dst addr, src port, dst port).  One direction is one key.
+ *
+ * Streams, per key, over its segments in capture order.
+ *   - A segment with SYN set whose seq differs from that of the key's latest earlier SYN
+ *     segment opens a new stream with base = seq + 1.  A SYN segment's own payload is ignored.
+ *     A SYN repeated with the same seq changes nothing.
+ *   - Segments before the key's first SYN belong to a stream without MGENX_TCP_SYN.  Its base
+ *     is the seq of the first of them that carries payload.
+ *   - A segment belongs to the stream open at its position.
+ *   - rel = (uint32)(seq - base).  A payload-carrying segment with rel >= 2^31 or
+ *     rel + len > 2^31 is stale.  It is counted in n_stale and contributes nothing.  A stream
+ *     holds at most 2 GiB.
+ *   - FIN and RST delimit nothing.
+ *   - A stream with no payload-carrying segment that is not stale still counts in n_streams,
+ *     with len 0.
+ *
+ * Content of a stream.
+ *   - Order its non-stale payload segments by (rel, capture index).
+ *   - Let E be the largest rel + len over the segments before a segment in that order (0 for
+ *     the first).  The segment contributes the piece [max(rel, E), rel + len) when that is not
+ *     empty.  Left-most start wins; a retransmission contributes nothing.
+ *   - The first segment in that order with rel > E is a hole.  The stream's len is E there, and
+ *     the flag MGENX_TCP_GAP is set.
+ *   - dropped is the sum of the piece lengths from that segment on.
+ *   - Without a hole, len is the final E.
+ *   - Resynchronising behind a hole is out of scope.  The framing of what follows is unknown.
+ *
+ * Layout.
+ *   - Streams are numbered by first_pkt, the capture index of their first segment of any kind.
+ *     n_segments counts a stream's segments of any kind.
+ *   - Each stream with len > 0 takes a slot of round16(len) bytes at
+ *     dev_buf + scratch_off + (sum of earlier slots).  The pad is zeroed.  off is absolute in
+ *     dev_buf (a stream of len 0: where its empty slot would start).
+ *   - scratch_bytes is the exact sum.
+ *   - dev_buf + scratch_off must be 16-byte aligned.  Every packet lies below scratch_off (one
+ *     reaching past it is not examined).
+ *
+ * Pieces.
+ *   - For every piece that ends at or below its stream's len, in stream order and then offset
+ *     order: dev_piece_end[k] is the absolute offset in dev_buf of the piece's end.
+ *   - These are strictly increasing over all k, because slots ascend.
+ *   - dev_piece_pkt[k] is the largest capture index among its stream's pieces 0..k.  This is
+ *     the packet at which every byte up to there had arrived.
+ *   - n_pieces <= n.  The caller gives arrays of n.
+ *
+ * Sizing, as mgenx_pcap_defrag.
+ *   - stats (host memory) is always filled.  The call is synchronous: one read-back.
+ *   - With stream_cap < n_streams, or a window below scratch_bytes, no output array, status or
+ *     scratch byte changes and MGENX_ENOSPC comes back.
+ * mgenx_pcapng_tcp takes the packet blocks and the data_off / cap_len of mgenx_pcapng_parse, as
+ * mgenx_pcapng_defrag does. */
+#define MGENX_PCAP_TCP 9          /* status: a TCP segment taken by mgenx_pcap_tcp */
+#define MGENX_TCP_SYN 0x1         /* stream flags: opened by a SYN */
+#define MGENX_TCP_GAP 0x2         /* cut at a hole: bytes past `len` were dropped */
+typedef struct {
+    mgenx_addr src, dst;
+    uint64_t off, len, dropped;
+    uint32_t first_pkt, n_segments, flags, rsv;
+} mgenx_tcp_stream;               /* 80 bytes */
+typedef struct {
+    uint64_t n_segments;     /* packets given MGENX_PCAP_TCP */
+    uint64_t n_streams;
+    uint64_t n_gap_streams;  /* streams with MGENX_TCP_GAP */
+    uint64_t n_stale;
+    uint64_t dropped_bytes;  /* sum of the streams' dropped */
+    uint64_t n_pieces;
+    uint64_t scratch_bytes;  /* the exact need: sum of round16(len) over the streams */
+} mgenx_tcp_stats;
+int mgenx_pcap_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                   const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                   uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                   uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                   void* stream);
+int mgenx_pcapng_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                     const uint64_t* dev_pkt_off, const uint64_t* dev_data_off,
+                     const uint32_t* dev_cap_len, uint32_t n, uint32_t link_type, uint32_t flags,
+                     uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                     uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                     void* stream);
+/* mgenx_tcp_frame: the rebuilt streams -> records, in completion order.
+ *   - Per stream, the records are those mgenx_stream_scan(MGENX_SCAN_TCP) finds in
+ *     [off, off + len) alone.  dev_stream_status[s] is that scan's status.  A record cut by the
+ *     stream's end is not a record.
+ *   - Per record, rec_pkt = dev_piece_pkt[k], where k is the first piece with
+ *     piece_end >= rec_off + rec_len.  rx_sec / rx_usec are that packet's (dev_pkt_rx_*: the
+ *     parse's per-packet times).  src is the stream's src.
+ *   - Output order is by (rec_pkt, stream number, offset).  Within a stream this is chain
+ *     order, because piece_pkt never decreases.  So dev_rec_pkt is non-decreasing and can be
+ *     mgenx_text_interleave's MGENX_TEXT_OWNER index as it is.
+ *   - Two passes.  *n_records (host memory) is always set.  The record arrays are written only
+ *     when it fits cap; dev_stream_status (n_streams bytes) always.  Synchronous.
+ *   - Streams of at least long_bytes go through the parallel scan of mgenx_stream_scan, one
+ *     stream at a time.  The others take one lane per stream, following offset += msg_len.
+ *     long_bytes 0 selects the default, 4 MiB. */
+int mgenx_tcp_frame(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                    const mgenx_tcp_stream* dev_streams, uint32_t n_streams,
+                    const uint64_t* dev_piece_end, const uint32_t* dev_piece_pkt,
+                    uint32_t n_pieces, const uint32_t* dev_pkt_rx_sec,
+                    const uint32_t* dev_pkt_rx_usec, uint64_t long_bytes, uint64_t* dev_rec_off,
+                    uint32_t* dev_rec_len, uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt,
+                    mgenx_addr* dev_rec_src, uint32_t* dev_rec_rx_sec, uint32_t* dev_rec_rx_usec,
+                    uint64_t cap, uint8_t* dev_stream_status, uint64_t* n_records, void* stream);
+
 /* ---- MgenMsg::ConvertBinaryLog: binary log -> text log (src/common/mgenMsg.cpp:1417-1900) --
  * mgenx_binlog_index (HOST memory, no device work) checks the header line ("mgen
  * version=<4|5> ... type=binary_log\n" and its NUL, :1437-1518) and walks the records

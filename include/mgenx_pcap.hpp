@@ -11,6 +11,13 @@
 //   mgenx_text_interleave (per packet: analytic REPORT, RECV, received REPORTs) -> D2H.
 // A pcapng capture (what Wireshark writes) differs only in its front end: mgenx_pcapng_index
 // (host, the block walk) and mgenx_pcapng_parse; Run tells the two by the first four bytes.
+// PcapOptions::tcp (not in the reference, which drops every packet that is not UDP) adds
+//   mgenx_pcap_tcp -> mgenx_tcp_frame -> mgenx_unpack_batch(MGENX_OPT_TCP) ->
+//   mgenx_log_recv_text(protocol TCP, RERR lines kept)
+// as one more source of the interleave: each record of a rebuilt TCP stream is logged at the
+// packet that completed it, after that packet's own lines.  Each record is unpacked into a
+// fresh message (the receiver's persistent rx_msg, mgenx_tcp_rx_persist, is not emulated);
+// the analytics stay UDP-only and REPORT items inside TCP payloads are not logged.
 // A few small values come back to the host between stages (flow count, report count, text
 // sizes); everything per packet stays on the device.
 #pragma once
@@ -31,6 +38,8 @@ struct PcapOptions {
   // not in the reference: rebuild fragmented IPv4 / IPv6 datagrams (mgenx_pcap_defrag)
   bool reassemble = false;
   double frag_timeout = 30.0;  // seconds a datagram may take to complete; 0 = no limit
+  // not in the reference: log the MGEN messages of TCP connections (mgenx_pcap_tcp)
+  bool tcp = false;
 };
 
 class Pcap2Mgen {
@@ -39,6 +48,9 @@ class Pcap2Mgen {
 
   // what the last run with PcapOptions::reassemble found (zeros before one)
   const mgenx_defrag_stats& defrag_stats() const { return defrag_stats_; }
+  // what the last run with PcapOptions::tcp found (zeros before one), and its record count
+  const mgenx_tcp_stats& tcp_stats() const { return tcp_stats_; }
+  uint64_t tcp_records() const { return tcp_records_; }
 
   // The log text of a pcap or pcapng file image (host memory); the first four bytes tell which
   // (a Section Header Block's type reads 0A 0D 0D 0A in either byte order).
@@ -54,16 +66,18 @@ class Pcap2Mgen {
     if (n == 0) return std::string();
     hipStream_t s = ctx_.stream();
     // the file image, then scratch for the packets a snapshot length cut (mgenx_pcap_snap),
-    // then, with reassemble, scratch for the rebuilt datagrams
+    // then, with reassemble, scratch for the rebuilt datagrams, then, with tcp, for the streams
     const uint64_t defrag_off = DefragOff(nbytes + info.snap_bytes);
-    const uint64_t total = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    const uint64_t used = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    const uint64_t tcp_off = TcpOff(used);
+    const uint64_t total = tcp_off ? tcp_off + nbytes : used;
     DeviceArray<uint8_t> buf(total);
     DeviceArray<uint64_t> pkt(n);
     check_hip(hipMemcpyAsync(buf.data(), file, nbytes, hipMemcpyHostToDevice, s), "H2D file");
     check_hip(hipMemcpyAsync(pkt.data(), offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, s),
               "H2D offsets");
     std::string out = RunDevice(buf.data(), nbytes, pkt.data(), n, info.link_type, info.flags,
-                                total, defrag_off);
+                                total, defrag_off, tcp_off);
     return out;
   }
 
@@ -72,9 +86,12 @@ class Pcap2Mgen {
   // PcapOptions::reassemble the defrag scratch is [defrag_off, buf_bytes) (16-byte aligned; the
   // file's size is always enough: a fragment's payload is shorter than its record) and the snap
   // scratch ends there; defrag_off 0: no defrag scratch, a capture that needs some throws.
+  // With PcapOptions::tcp the stream scratch is [tcp_off, buf_bytes) in the same way (the file's
+  // size is enough: a segment's payload is shorter than its record by more than 16 bytes) and
+  // the scratch before it ends there.
   std::string RunDevice(uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_pkt, uint32_t n,
                         uint32_t link_type, uint32_t flags, uint64_t buf_bytes = 0,
-                        uint64_t defrag_off = 0) {
+                        uint64_t defrag_off = 0, uint64_t tcp_off = 0) {
     mgenx_ctx* c = ctx_.get();
     hipStream_t s = ctx_.stream();
     DeviceArray<uint64_t> udp_off(n);
@@ -87,18 +104,23 @@ class Pcap2Mgen {
                                 rx_usec.data(), status.data(), s),
                "mgenx_pcap_parse");
     if (buf_bytes < nbytes) buf_bytes = nbytes;
-    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : buf_bytes;
+    const uint64_t tcp_at = o_.tcp && tcp_off ? tcp_off : buf_bytes;
+    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : tcp_at;
     if (snap_end > nbytes)
       ctx_.Check(mgenx_pcap_snap(c, d_buf, nbytes, snap_end, d_pkt, n, flags, status.data(),
                                  udp_off.data(), udp_len.data(), s),
                  "mgenx_pcap_snap");
     if (o_.reassemble)
-      Defragged(mgenx_pcap_defrag(c, d_buf, snap_end, buf_bytes, d_pkt, n, link_type, flags,
+      Defragged(mgenx_pcap_defrag(c, d_buf, snap_end, tcp_at, d_pkt, n, link_type, flags,
                                   FragTimeoutUs(), rx_sec.data(), rx_usec.data(), status.data(),
                                   udp_off.data(), udp_len.data(), src.data(), &defrag_stats_, s),
-                buf_bytes - snap_end);
+                tcp_at - snap_end);
+    TcpRecords tr;
+    if (o_.tcp)
+      TcpStreams(d_buf, tcp_at, buf_bytes, d_pkt, nullptr, nullptr, n, link_type, flags,
+                 status.data(), rx_sec.data(), rx_usec.data(), tr);
     nbytes = buf_bytes;  // the records may now reach into the scratch
-    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
+    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec, tr);
   }
 
   // The same over a resident pcapng image: d_pkt / d_pkt_if / d_ifaces as mgenx_pcapng_index
@@ -106,7 +128,8 @@ class Pcap2Mgen {
   std::string RunDeviceNg(uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_pkt,
                           const uint32_t* d_pkt_if, uint32_t n, const mgenx_pcapng_if* d_ifaces,
                           uint32_t n_ifaces, uint32_t link_type, uint32_t flags,
-                          uint64_t buf_bytes = 0, uint64_t defrag_off = 0) {
+                          uint64_t buf_bytes = 0, uint64_t defrag_off = 0,
+                          uint64_t tcp_off = 0) {
     mgenx_ctx* c = ctx_.get();
     hipStream_t s = ctx_.stream();
     DeviceArray<uint64_t> udp_off(n), data_off(n);
@@ -120,19 +143,24 @@ class Pcap2Mgen {
                                   data_off.data(), cap_len.data(), s),
                "mgenx_pcapng_parse");
     if (buf_bytes < nbytes) buf_bytes = nbytes;
-    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : buf_bytes;
+    const uint64_t tcp_at = o_.tcp && tcp_off ? tcp_off : buf_bytes;
+    const uint64_t snap_end = o_.reassemble && defrag_off ? defrag_off : tcp_at;
     if (snap_end > nbytes)
       ctx_.Check(mgenx_pcapng_snap(c, d_buf, nbytes, snap_end, data_off.data(), cap_len.data(),
                                    n, status.data(), udp_off.data(), udp_len.data(), s),
                  "mgenx_pcapng_snap");
     if (o_.reassemble)
-      Defragged(mgenx_pcapng_defrag(c, d_buf, snap_end, buf_bytes, d_pkt, data_off.data(),
+      Defragged(mgenx_pcapng_defrag(c, d_buf, snap_end, tcp_at, d_pkt, data_off.data(),
                                     cap_len.data(), n, link_type, flags, FragTimeoutUs(),
                                     rx_sec.data(), rx_usec.data(), status.data(), udp_off.data(),
                                     udp_len.data(), src.data(), &defrag_stats_, s),
-                buf_bytes - snap_end);
+                tcp_at - snap_end);
+    TcpRecords tr;
+    if (o_.tcp)
+      TcpStreams(d_buf, tcp_at, buf_bytes, d_pkt, data_off.data(), cap_len.data(), n, link_type,
+                 flags, status.data(), rx_sec.data(), rx_usec.data(), tr);
     nbytes = buf_bytes;
-    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec);
+    return Finish(d_buf, nbytes, n, udp_off, udp_len, src, ttl, rx_sec, rx_usec, tr);
   }
 
  private:
@@ -150,7 +178,9 @@ class Pcap2Mgen {
     if (n == 0) return std::string();
     hipStream_t s = ctx_.stream();
     const uint64_t defrag_off = DefragOff(nbytes + info.snap_bytes);
-    const uint64_t total = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    const uint64_t used = defrag_off ? defrag_off + nbytes : nbytes + info.snap_bytes;
+    const uint64_t tcp_off = TcpOff(used);
+    const uint64_t total = tcp_off ? tcp_off + nbytes : used;
     DeviceArray<uint8_t> buf(total);
     DeviceArray<uint64_t> pkt(n);
     DeviceArray<uint32_t> pkt_if(n);
@@ -165,12 +195,73 @@ class Pcap2Mgen {
                              hipMemcpyHostToDevice, s),
               "H2D interface table");
     return RunDeviceNg(buf.data(), nbytes, pkt.data(), pkt_if.data(), n, d_ifs.data(),
-                       info.n_ifaces, info.link_type, info.flags, total, defrag_off);
+                       info.n_ifaces, info.link_type, info.flags, total, defrag_off, tcp_off);
   }
 
   // where Run puts the defrag scratch: 16-byte aligned after the snap scratch (0: none)
   uint64_t DefragOff(uint64_t used) const {
     return o_.reassemble ? (used + 15) & ~(uint64_t)15 : 0;
+  }
+
+  // where Run puts the stream scratch: 16-byte aligned after everything else (0: none)
+  uint64_t TcpOff(uint64_t used) const { return o_.tcp ? (used + 15) & ~(uint64_t)15 : 0; }
+
+  // the records of the capture's TCP streams, in completion order
+  struct TcpRecords {
+    uint32_t n = 0;
+    DeviceArray<uint64_t> off;
+    DeviceArray<uint32_t> len, stream, pkt, rx_sec, rx_usec;
+    DeviceArray<mgenx_addr> src;
+  };
+
+  // mgenx_pcap_tcp (d_data_off null) or mgenx_pcapng_tcp, then mgenx_tcp_frame: each sized by a
+  // first call and repeated once when its table was too small
+  void TcpStreams(uint8_t* d_buf, uint64_t tcp_at, uint64_t buf_bytes, const uint64_t* d_pkt,
+                  const uint64_t* d_data_off, const uint32_t* d_cap_len, uint32_t n,
+                  uint32_t link_type, uint32_t flags, uint8_t* d_status, const uint32_t* d_rx_sec,
+                  const uint32_t* d_rx_usec, TcpRecords& r) {
+    mgenx_ctx* c = ctx_.get();
+    hipStream_t s = ctx_.stream();
+    DeviceArray<mgenx_tcp_stream> streams;
+    DeviceArray<uint64_t> piece_end(n);
+    DeviceArray<uint32_t> piece_pkt(n);
+    uint32_t cap = n < 4096u ? n : 4096u;
+    tcp_records_ = 0;
+    int rc = MGENX_OK;
+    for (int pass = 0; pass < 2; pass++) {
+      streams.Resize(cap);
+      rc = d_data_off
+               ? mgenx_pcapng_tcp(c, d_buf, tcp_at, buf_bytes, d_pkt, d_data_off, d_cap_len, n,
+                                  link_type, flags, d_status, streams.data(), cap,
+                                  piece_end.data(), piece_pkt.data(), &tcp_stats_, s)
+               : mgenx_pcap_tcp(c, d_buf, tcp_at, buf_bytes, d_pkt, n, link_type, flags, d_status,
+                                streams.data(), cap, piece_end.data(), piece_pkt.data(),
+                                &tcp_stats_, s);
+      if (rc != MGENX_ENOSPC || tcp_stats_.n_streams <= cap) break;
+      cap = (uint32_t)tcp_stats_.n_streams;
+    }
+    if (rc == MGENX_ENOSPC)
+      throw Error("pcap2mgen: the TCP streams need " + std::to_string(tcp_stats_.scratch_bytes) +
+                  " bytes of scratch, the buffer has " + std::to_string(buf_bytes - tcp_at));
+    ctx_.Check(rc, "mgenx_pcap_tcp");
+    const uint32_t n_streams = (uint32_t)tcp_stats_.n_streams;
+    DeviceArray<uint8_t> stream_status(n_streams);
+    // two records per piece first: enough unless the messages are much shorter than the segments
+    uint64_t rcap = 2 * tcp_stats_.n_pieces > 1024 ? 2 * tcp_stats_.n_pieces : 1024, total = 0;
+    for (int pass = 0; pass < 2; pass++) {
+      r.off.Resize(rcap); r.len.Resize(rcap); r.stream.Resize(rcap); r.pkt.Resize(rcap);
+      r.src.Resize(rcap); r.rx_sec.Resize(rcap); r.rx_usec.Resize(rcap);
+      ctx_.Check(mgenx_tcp_frame(c, d_buf, buf_bytes, streams.data(), n_streams, piece_end.data(),
+                                 piece_pkt.data(), (uint32_t)tcp_stats_.n_pieces, d_rx_sec,
+                                 d_rx_usec, 0, r.off.data(), r.len.data(), r.stream.data(),
+                                 r.pkt.data(), r.src.data(), r.rx_sec.data(), r.rx_usec.data(),
+                                 rcap, stream_status.data(), &total, s),
+                 "mgenx_tcp_frame");
+      if (total <= rcap) break;
+      rcap = total;
+    }
+    r.n = (uint32_t)total;
+    tcp_records_ = total;
   }
 
   int64_t FragTimeoutUs() const {
@@ -188,7 +279,7 @@ class Pcap2Mgen {
   std::string Finish(uint8_t* d_buf, uint64_t nbytes, uint32_t n, DeviceArray<uint64_t>& udp_off,
                      DeviceArray<uint32_t>& udp_len, DeviceArray<mgenx_addr>& src,
                      DeviceArray<int32_t>& ttl, DeviceArray<uint32_t>& rx_sec,
-                     DeviceArray<uint32_t>& rx_usec) {
+                     DeviceArray<uint32_t>& rx_usec, const TcpRecords& tr) {
     mgenx_ctx* c = ctx_.get();
     hipStream_t s = ctx_.stream();
     Columns col(n);
@@ -282,6 +373,23 @@ class Pcap2Mgen {
       });
       srcs.push_back(Src(MGENX_TEXT_OWNER, rrtext.data(), rrline.data(), n_reps,
                          reinterpret_cast<const uint32_t*>(pairs.data()), 4));
+    }
+    // the records of TCP streams: each a fresh MgenMsg under the TCP receive rules with the CRC
+    // check; an error logs RERR (MgenTcpTransport::OnRecvMsg, mgenTransport.cpp:1736-1750)
+    DeviceArray<char> ttext;
+    DeviceArray<uint64_t> tline(tr.n + 1);
+    Columns tcol(tr.n);
+    if (tr.n && o_.log_rx) {
+      ctx_.Check(mgenx_unpack_batch(c, d_buf, nbytes, tr.off.data(), 0, tr.len.data(), 0, tr.n,
+                                    &tcol.cols, MGENX_OPT_TCP, s),
+                 "mgenx_unpack_batch");
+      TwoPass(ttext, tline.data(), tr.n, [&](char* t, uint64_t cp) {
+        return mgenx_log_recv_text(c, d_buf, tr.off.data(), 0, &tcol.cols, tr.src.data(),
+                                   tr.rx_sec.data(), tr.rx_usec.data(), nullptr, tr.n,
+                                   MGENX_PROTO_TCP, lopts | MGENX_LOG_NO_DATA, t, cp,
+                                   tline.data(), s);
+      });
+      srcs.push_back(Src(MGENX_TEXT_OWNER, ttext.data(), tline.data(), tr.n, tr.pkt.data(), 1));
     }
     if (srcs.empty()) return std::string();
     DeviceArray<char> all;
@@ -382,6 +490,8 @@ class Pcap2Mgen {
   Context& ctx_;
   PcapOptions o_;
   mgenx_defrag_stats defrag_stats_ = {};
+  mgenx_tcp_stats tcp_stats_ = {};
+  uint64_t tcp_records_ = 0;
 };
 
 }  // namespace mgenx

@@ -30,6 +30,7 @@ from ._abi import (  # noqa: F401
     PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE, PCAPNG_TSRESOL, PCAPNG_CAPLEN,
     FLOW_DIST_BINS, FLOW_DIST_DTYPE,
     ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
+    PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_flow_dist_init", "mgenx_flow_dist", "mgenx_flow_dist_quantiles",
     "mgenx_flow_dist_bin", "mgenx_flow_dist_bin_lo",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
+    "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -126,6 +128,12 @@ def load(diag: bool = False):
                                     P, P, ctypes.POINTER(DefragStats), P]
     L.mgenx_pcapng_defrag.argtypes = [P, P, u64, u64, P, P, P, u32, u32, u32, ctypes.c_int64, P,
                                       P, P, P, P, P, ctypes.POINTER(DefragStats), P]
+    L.mgenx_pcap_tcp.argtypes = [P, P, u64, u64, P, u32, u32, u32, P, P, u32, P, P,
+                                 ctypes.POINTER(TcpStats), P]
+    L.mgenx_pcapng_tcp.argtypes = [P, P, u64, u64, P, P, P, u32, u32, u32, P, P, u32, P, P,
+                                   ctypes.POINTER(TcpStats), P]
+    L.mgenx_tcp_frame.argtypes = [P, P, u64, P, u32, P, P, u32, P, P, u64, P, P, P, P, P, P, P,
+                                  u64, P, ctypes.POINTER(u64), P]
     L.mgenx_binlog_index.argtypes = [P, u64, P, u64, ctypes.POINTER(BinlogInfo)]
     L.mgenx_convert_binary_log.argtypes = [P, P, u64, P, u32, u32, u32, P, u64, P, P]
     L.mgenx_text_index.argtypes = [P, P, u64, P, u64, P, P]
@@ -810,6 +818,81 @@ class Engine:
         if rc != ENOSPC:
             self._check(rc, "mgenx_pcapng_defrag")
         return rc == 0, st
+
+    def pcap_tcp(self, buf, scratch_off, pkt_off, n, link_type, flags, parsed, stream_cap=None,
+                 out=None):
+        """mgenx_pcap_tcp (mgenx_pcapng_tcp when `parsed` is pcapng_parse's dict): rebuild the
+        TCP streams among the packets of `parsed` into buf[scratch_off:], in place.  Returns
+        (fits, TcpStats, streams, piece_end, piece_pkt): the stream table as a uint8 tensor of
+        stream_cap x 80 (TCP_STREAM_DTYPE), the piece table as int64 / int32 tensors of n.
+        fits False = the window or the stream table is too small and nothing was changed (an
+        empty window with stream_cap 0 sizes both).  out: (streams, piece_end, piece_pkt)
+        tensors to fill.  Synchronous."""
+        torch = self.torch
+        dev = buf.device
+        if out is not None:
+            streams, piece_end, piece_pkt = out
+            stream_cap = streams.numel() // 80
+        else:
+            stream_cap = n if stream_cap is None else stream_cap
+            streams = torch.zeros(max(stream_cap, 1) * 80, dtype=torch.uint8, device=dev)
+            piece_end = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+            piece_pkt = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        st = TcpStats()
+        tail = (_ptr(parsed["status"]), _ptr(streams), stream_cap, _ptr(piece_end),
+                _ptr(piece_pkt), ctypes.byref(st), _stream(self.device))
+        if "data_off" in parsed:
+            what = "mgenx_pcapng_tcp"
+            rc = self.lib.mgenx_pcapng_tcp(
+                self.ctx, _ptr(buf), scratch_off, buf.numel(), _ptr(pkt_off),
+                _ptr(parsed["data_off"]), _ptr(parsed["cap_len"]), n, link_type, flags, *tail)
+        else:
+            what = "mgenx_pcap_tcp"
+            rc = self.lib.mgenx_pcap_tcp(self.ctx, _ptr(buf), scratch_off, buf.numel(),
+                                         _ptr(pkt_off), n, link_type, flags, *tail)
+        if rc != ENOSPC:
+            self._check(rc, what)
+        return rc == 0, st, streams, piece_end, piece_pkt
+
+    def tcp_frame(self, buf, streams, n_streams, piece_end, piece_pkt, n_pieces, rx_sec, rx_usec,
+                  long_bytes=0, cap=None):
+        """mgenx_tcp_frame: the records of the streams pcap_tcp rebuilt, in completion order.
+        Returns (dict of device tensors rec_off, rec_len, rec_stream, rec_pkt, rec_src
+        (n x 20), rx_sec, rx_usec, each cut to the record count; stream_status; n_records).
+        cap: the capacity tried first (None: two records per piece; a second call follows
+        when the records do not fit); with a cap given, a result that does not fit
+        comes back as (None, stream_status, n_records)."""
+        torch = self.torch
+        dev = buf.device
+        status = torch.zeros(max(n_streams, 1), dtype=torch.uint8, device=dev)
+        total = ctypes.c_uint64(0)
+        retry = cap is None
+        if cap is None:
+            cap = max(1024, 2 * n_pieces)
+        for _ in range(2):
+            m = max(cap, 1)
+            o = {"rec_off": torch.empty(m, dtype=torch.int64, device=dev),
+                 "rec_len": torch.empty(m, dtype=torch.int32, device=dev),
+                 "rec_stream": torch.empty(m, dtype=torch.int32, device=dev),
+                 "rec_pkt": torch.empty(m, dtype=torch.int32, device=dev),
+                 "rec_src": torch.empty(m * 20, dtype=torch.uint8, device=dev),
+                 "rx_sec": torch.empty(m, dtype=torch.int32, device=dev),
+                 "rx_usec": torch.empty(m, dtype=torch.int32, device=dev)}
+            rc = self.lib.mgenx_tcp_frame(
+                self.ctx, _ptr(buf), buf.numel(), _ptr(streams), n_streams, _ptr(piece_end),
+                _ptr(piece_pkt), n_pieces, _ptr(rx_sec), _ptr(rx_usec), long_bytes,
+                _ptr(o["rec_off"]), _ptr(o["rec_len"]), _ptr(o["rec_stream"]), _ptr(o["rec_pkt"]),
+                _ptr(o["rec_src"]), _ptr(o["rx_sec"]), _ptr(o["rx_usec"]), cap, _ptr(status),
+                ctypes.byref(total), _stream(self.device))
+            self._check(rc, "mgenx_tcp_frame")
+            k = int(total.value)
+            if k <= cap:
+                return ({name: t[:k * 20] if name == "rec_src" else t[:k]
+                         for name, t in o.items()}, status[:n_streams], k)
+            if not retry:
+                break
+            cap = k
+        return None, status[:n_streams], int(total.value)
 
     def flow_export(self, flows, n_flows, out=None):
         if out is None:

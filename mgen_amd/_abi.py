@@ -201,6 +201,24 @@ class DefragStats(ctypes.Structure):   # mgenx_defrag_stats
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+PCAP_TCP = 9              # MGENX_PCAP_TCP
+TCP_SYN, TCP_GAP = 0x1, 0x2   # MGENX_TCP_SYN / _GAP (mgenx_tcp_stream.flags)
+TCP_STREAM_DTYPE = np.dtype([    # mgenx_tcp_stream
+    ("src", ADDR_DTYPE), ("dst", ADDR_DTYPE), ("off", "<u8"), ("len", "<u8"), ("dropped", "<u8"),
+    ("first_pkt", "<u4"), ("n_segments", "<u4"), ("flags", "<u4"), ("rsv", "<u4")])
+assert TCP_STREAM_DTYPE.itemsize == 80
+
+
+class TcpStats(ctypes.Structure):      # mgenx_tcp_stats
+    _fields_ = [("n_segments", ctypes.c_uint64), ("n_streams", ctypes.c_uint64),
+                ("n_gap_streams", ctypes.c_uint64), ("n_stale", ctypes.c_uint64),
+                ("dropped_bytes", ctypes.c_uint64), ("n_pieces", ctypes.c_uint64),
+                ("scratch_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BinlogInfo(ctypes.Structure):    # mgenx_binlog_info
     _fields_ = [("n_records", ctypes.c_uint64), ("consumed", ctypes.c_uint64),
                 ("status", ctypes.c_int32), ("version", ctypes.c_uint32)]

@@ -103,6 +103,28 @@ extern "C" int mgenx_defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_of
                                 uint64_t* dev_udp_off, uint32_t* dev_udp_len, mgenx_addr* dev_src,
                                 mgenx_defrag_stats* stats, hipStream_t stream, char* err,
                                 size_t errn);
+extern "C" size_t mgenx_pcap_tcp_ws(uint32_t n);
+extern "C" int mgenx_pcap_tcp_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off,
+                                  uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                                  const uint64_t* dev_data_off, const uint32_t* dev_cap_len,
+                                  uint32_t n, uint32_t link_type, uint32_t flags,
+                                  uint8_t* dev_status, mgenx_tcp_stream* dev_streams,
+                                  uint32_t stream_cap, uint64_t* dev_piece_end,
+                                  uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                                  hipStream_t stream, char* err, size_t errn);
+extern "C" size_t mgenx_tcp_frame_ws(uint32_t n_streams, uint64_t cap);
+extern "C" int mgenx_tcp_frame_run(void* mem, void* scan_ws, const uint8_t* dev_buf,
+                                   uint64_t buf_bytes, const mgenx_tcp_stream* dev_streams,
+                                   uint32_t n_streams, const uint64_t* dev_piece_end,
+                                   const uint32_t* dev_piece_pkt, uint32_t n_pieces,
+                                   const uint32_t* dev_pkt_rx_sec,
+                                   const uint32_t* dev_pkt_rx_usec, uint64_t long_bytes,
+                                   uint64_t* dev_rec_off, uint32_t* dev_rec_len,
+                                   uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt,
+                                   mgenx_addr* dev_rec_src, uint32_t* dev_rec_rx_sec,
+                                   uint32_t* dev_rec_rx_usec, uint64_t cap,
+                                   uint8_t* dev_stream_status, uint64_t* n_records,
+                                   hipStream_t stream, char* err, size_t errn);
 extern "C" int mgenx_log_recv_run(void* ws, bool binary, const uint8_t* slab,
                                   uint64_t slab_bytes, const uint64_t* rec_off,
                                   const uint32_t* rec_len,
@@ -216,6 +238,8 @@ struct mgenx_ctx {
   mgenx_grow bl[5];                // mgenx_convert_binary_log: records, lines, pairs, report text
   mgenx_grow snap;                 // mgenx_pcap_snap: per-packet sizes + scan scratch
   mgenx_grow defrag;               // mgenx_pcap_defrag: per-packet arrays + sort / scan scratch
+  mgenx_grow ptcp;                 // mgenx_pcap_tcp: per-packet arrays + sort / scan scratch
+  mgenx_grow tcpf;                 // mgenx_tcp_frame: per-record arrays + sort scratch
   mgenx_grow lp;                   // mgenx_text_index / mgenx_log_parse_text: per-line scratch
   bool rand_ready = false;
   uint32_t rand_time = 0;
@@ -412,6 +436,8 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   for (mgenx_grow& g : c->bl) g.release();
   c->snap.release();
   c->defrag.release();
+  c->ptcp.release();
+  c->tcpf.release();
   c->lp.release();
   for (void* p : ps) mgenx::dev_free(p);
   delete c;
@@ -1660,6 +1686,78 @@ int mgenx_pcapng_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
   return pcap_defrag_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
                          dev_cap_len, n, link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec,
                          dev_status, dev_udp_off, dev_udp_len, dev_src, stats, stream);
+}
+
+// both TCP reassemblies: dev_data_off null = classic records, else pcapng packet blocks
+static int pcap_tcp_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                        uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                        const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                        uint32_t link_type, uint32_t flags, uint8_t* dev_status,
+                        mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                        uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                        void* stream) {
+  if (!ctx || !stats || buf_bytes < scratch_off || n > 0x7FFFFFFEu) return MGENX_EINVAL;
+  memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_status || (stream_cap && !dev_streams) ||
+      !dev_piece_end || !dev_piece_pkt)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  void* m = ctx->ptcp.get(mgenx_pcap_tcp_ws(n));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_tcp workspace");
+  return mgenx_pcap_tcp_run(m, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                            dev_cap_len, n, link_type, flags, dev_status, dev_streams,
+                            stream_cap, dev_piece_end, dev_piece_pkt, stats,
+                            (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_pcap_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                   const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                   uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                   uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                   void* stream) {
+  return pcap_tcp_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, nullptr, nullptr, n,
+                      link_type, flags, dev_status, dev_streams, stream_cap, dev_piece_end,
+                      dev_piece_pkt, stats, stream);
+}
+
+int mgenx_pcapng_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                     const uint64_t* dev_pkt_off, const uint64_t* dev_data_off,
+                     const uint32_t* dev_cap_len, uint32_t n, uint32_t link_type, uint32_t flags,
+                     uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                     uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                     void* stream) {
+  if (n && (!dev_data_off || !dev_cap_len)) return MGENX_EINVAL;
+  return pcap_tcp_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                      dev_cap_len, n, link_type, flags, dev_status, dev_streams, stream_cap,
+                      dev_piece_end, dev_piece_pkt, stats, stream);
+}
+
+int mgenx_tcp_frame(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                    const mgenx_tcp_stream* dev_streams, uint32_t n_streams,
+                    const uint64_t* dev_piece_end, const uint32_t* dev_piece_pkt,
+                    uint32_t n_pieces, const uint32_t* dev_pkt_rx_sec,
+                    const uint32_t* dev_pkt_rx_usec, uint64_t long_bytes, uint64_t* dev_rec_off,
+                    uint32_t* dev_rec_len, uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt,
+                    mgenx_addr* dev_rec_src, uint32_t* dev_rec_rx_sec, uint32_t* dev_rec_rx_usec,
+                    uint64_t cap, uint8_t* dev_stream_status, uint64_t* n_records, void* stream) {
+  if (!ctx || !n_records || n_streams > 0x7FFFFFFEu || cap > 0x7FFFFFFEu) return MGENX_EINVAL;
+  *n_records = 0;
+  if (n_streams == 0) return MGENX_OK;
+  if (!dev_buf || !dev_streams || !dev_stream_status || (n_pieces && (!dev_piece_end ||
+      !dev_piece_pkt)) || !dev_pkt_rx_sec || !dev_pkt_rx_usec ||
+      (cap && (!dev_rec_off || !dev_rec_len || !dev_rec_stream || !dev_rec_pkt || !dev_rec_src ||
+               !dev_rec_rx_sec || !dev_rec_rx_usec)))
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (!ctx->scan_ws) ctx->scan_ws = mgenx_scan_ws_new();
+  void* m = ctx->tcpf.get(mgenx_tcp_frame_ws(n_streams, cap));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "tcp_frame workspace");
+  return mgenx_tcp_frame_run(m, ctx->scan_ws, dev_buf, buf_bytes, dev_streams, n_streams, dev_piece_end,
+                             dev_piece_pkt, n_pieces, dev_pkt_rx_sec, dev_pkt_rx_usec, long_bytes,
+                             dev_rec_off, dev_rec_len, dev_rec_stream, dev_rec_pkt, dev_rec_src,
+                             dev_rec_rx_sec, dev_rec_rx_usec, cap, dev_stream_status, n_records,
+                             (hipStream_t)stream, ctx->err, sizeof(ctx->err));
 }
 
 // ---- ConvertBinaryLog (mgenMsg.cpp:1417-1900) ----

@@ -17,6 +17,15 @@ Here the whole file goes to HBM once and every stage is one batch call of the C 
 mgenx_pcapng_defrag after the snap step: fragmented IPv4 / IPv6 datagrams are rebuilt in
 scratch after the file image and logged at their completing fragment's position.
 
+``tcp`` (not in the reference, which drops every packet that is not UDP; off by default) adds
+mgenx_pcap_tcp / mgenx_pcapng_tcp -> mgenx_tcp_frame -> mgenx_unpack_batch (MGENX_OPT_TCP) ->
+mgenx_log_recv_text (protocol 2, RERR lines kept): the byte stream of every TCP connection is
+rebuilt in a further scratch window, framed into MGEN records, and each record is logged at the
+position of the packet that completed it, after that packet's own lines.  Every record is
+unpacked into a fresh message (the receiver's persistent rx_msg, mgenx_tcp_rx_persist, is not
+emulated offline); ``analytic`` stays UDP-only, REPORT items inside TCP payloads are not
+logged, and IP-fragmented TCP and IPv6 extension headers are not followed.
+
 Options mirror the reference's command line (``-analytic``/``-report``, ``+rxlog on|off``,
 ``+window``); ``trace`` (MAC addresses in front of each line) is not supported.
 """
@@ -25,8 +34,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import (DATA_CONTROLLER, FLOW_REPORT_DTYPE, LOG_EPOCH, LOG_NO_DATA, LOG_SKIP_ERR,
-               OPT_SKIP_CRC, PCAP_NG, TEXT_OWNER, TEXT_PER_RECORD, TEXT_SCATTER, Engine, MgenxError,
-               is_pcapng, pcap_index, pcapng_index)
+               OPT_SKIP_CRC, OPT_TCP, PCAP_NG, TEXT_OWNER, TEXT_PER_RECORD, TEXT_SCATTER, Engine,
+               MgenxError, is_pcapng, pcap_index, pcapng_index)
 
 
 def _quantized_window(window: float) -> float:
@@ -54,8 +63,11 @@ class Pcap2Mgen:
 
     def __init__(self, engine: Engine, analytics: bool = False, log_rx: bool = True,
                  window: float = 1.0, epoch: bool = False, reassemble: bool = False,
-                 frag_timeout: float = 30.0):
+                 frag_timeout: float = 30.0, tcp: bool = False):
         self.eng = engine
+        self.tcp = tcp
+        self.last_tcp_stats = None            # TcpStats of the last run with tcp
+        self.last_tcp_records = 0             # records framed by the last run with tcp
         self.reassemble = reassemble
         self.frag_timeout = frag_timeout      # seconds; 0 = fragments never expire
         self.last_defrag_stats = None         # DefragStats of the last reassembling run
@@ -70,7 +82,9 @@ class Pcap2Mgen:
         the info is a PcapngInfo with two more attributes for run_device's `ng`, pkt_if and
         ifaces (device tensors: each packet's interface row, the interface table).
         With reassemble the buffer also holds the defrag scratch, from info.defrag_off on:
-        as many bytes as the file (each fragment's payload is shorter than its record)."""
+        as many bytes as the file (each fragment's payload is shorter than its record).
+        With tcp a further window of as many bytes follows, from info.tcp_off on (each
+        segment's payload is shorter than its record by more than 16 bytes)."""
         torch = self.eng.torch
         b = np.frombuffer(bytes(file), np.uint8) if not isinstance(file, np.ndarray) else file
         dev = f"cuda:{self.eng.device}"
@@ -87,6 +101,10 @@ class Pcap2Mgen:
         if self.reassemble:
             info.defrag_off = (size + 15) & ~15
             size = info.defrag_off + b.size
+        info.tcp_off = None
+        if self.tcp:
+            info.tcp_off = (size + 15) & ~15
+            size = info.tcp_off + b.size
         buf = torch.zeros(size, dtype=torch.uint8, device=dev)
         buf[:b.size] = torch.from_numpy(b.copy()).to(dev)
         pkt_off = torch.from_numpy(offs.view(np.int64).copy()).to(dev)
@@ -97,24 +115,28 @@ class Pcap2Mgen:
         file_bytes = info.file_bytes
         ng = (info.pkt_if, info.ifaces) if info.flags & PCAP_NG else None
         text, _ = self.run_device(buf, pkt_off, int(info.n_records), info.link_type, info.flags,
-                                  file_bytes=file_bytes, ng=ng, defrag_off=info.defrag_off)
+                                  file_bytes=file_bytes, ng=ng, defrag_off=info.defrag_off,
+                                  tcp_off=info.tcp_off)
         return text.cpu().numpy().tobytes()
 
     def run_device(self, buf, pkt_off, n, link_type, flags, file_bytes=None, ng=None,
-                   defrag_off=None):
+                   defrag_off=None, tcp_off=None):
         """The device pipeline over a resident file: (text tensor, per-packet offsets).
         file_bytes: the file image's size when buf has scratch after it for snapped packets
         (None: no scratch; packets cut by the snapshot length are skipped).
         ng: for a pcapng capture, (pkt_if, ifaces) on the device -- pkt_off then holds the
         packet blocks' offsets (mgenx_pcapng_index).
         defrag_off: with reassemble, where the defrag scratch starts in buf (the snap scratch
-        then ends there); None: no scratch, and a capture with fragments to rebuild raises."""
+        then ends there); None: no scratch, and a capture with fragments to rebuild raises.
+        tcp_off: with tcp, where the stream scratch starts in buf (the scratch before it ends
+        there); None: no scratch, and a capture with TCP payload raises."""
         eng, torch = self.eng, self.eng.torch
         dev = buf.device
         if n == 0:
             return torch.empty(0, dtype=torch.uint8, device=dev), torch.zeros(
                 1, dtype=torch.int64, device=dev)
-        snap_end = buf.numel() if defrag_off is None else defrag_off
+        tcp_at = buf.numel() if tcp_off is None else tcp_off
+        snap_end = tcp_at if defrag_off is None else defrag_off
         snap = file_bytes is not None and file_bytes < snap_end
         if ng is not None:
             pkt_if, ifaces = ng
@@ -128,12 +150,14 @@ class Pcap2Mgen:
                 eng.pcap_snap(buf, file_bytes, pkt_off, n, flags, p, buf_bytes=snap_end)
         if self.reassemble:
             defrag = eng.pcap_defrag if ng is None else eng.pcapng_defrag
-            fits, st = defrag(buf, snap_end, pkt_off, n, link_type, flags, p,
+            fits, st = defrag(buf[:tcp_at], snap_end, pkt_off, n, link_type, flags, p,
                               timeout_us=round(self.frag_timeout * 1e6))
             self.last_defrag_stats = st
             if not fits:
                 raise MgenxError(f"pcap2mgen: reassembly needs {st.scratch_bytes} bytes of "
-                                 f"scratch, the buffer has {buf.numel() - snap_end}")
+                                 f"scratch, the buffer has {tcp_at - snap_end}")
+        tcp_recs = self._tcp_records(buf, tcp_at, pkt_off, n, link_type, flags, p) if self.tcp \
+            else None
         cols = eng.unpack(buf, n, rec_off=p["udp_off"], rec_len=p["udp_len"], opts=OPT_SKIP_CRC,
                           ext=True)
         sources = []
@@ -199,10 +223,41 @@ class Pcap2Mgen:
             rr_text, rr_line = eng.log_report_recv_text(buf, reps, n_reps, p["src"], p["rx_sec"],
                                                         p["rx_usec"], opts=self.opts)
             sources.append((TEXT_OWNER, rr_text, rr_line, n_reps, reps.view(torch.int32), 4))
+        if tcp_recs is not None and self.log_rx:
+            # each record a fresh MgenMsg, TCP receive rules and CRC check; an error logs RERR
+            # (MgenTcpTransport::OnRecvMsg, mgenTransport.cpp:1736-1750)
+            r, k = tcp_recs
+            tcols = eng.unpack(buf, k, rec_off=r["rec_off"], rec_len=r["rec_len"], opts=OPT_TCP,
+                               ext=True)
+            ttext, tline = eng.log_recv_text(buf, k, tcols, r["rec_src"], r["rx_sec"],
+                                             r["rx_usec"], rec_off=r["rec_off"], ttl=None,
+                                             protocol=2, opts=self.opts | LOG_NO_DATA)
+            sources.append((TEXT_OWNER, ttext, tline, k, r["rec_pkt"], 1))
         if not sources:
             return torch.empty(0, dtype=torch.uint8, device=dev), torch.zeros(
                 n + 1, dtype=torch.int64, device=dev)
         return eng.text_interleave(sources, n)
+
+    def _tcp_records(self, buf, tcp_at, pkt_off, n, link_type, flags, p):
+        """pcap_tcp + tcp_frame over the parsed packets: (record arrays, count), or None when
+        the capture holds no TCP record."""
+        eng = self.eng
+        cap = min(n, 4096)
+        for _ in range(2):
+            fits, st, streams, piece_end, piece_pkt = eng.pcap_tcp(
+                buf, tcp_at, pkt_off, n, link_type, flags, p, stream_cap=cap)
+            if fits or st.n_streams <= cap:
+                break
+            cap = int(st.n_streams)
+        self.last_tcp_stats = st
+        self.last_tcp_records = 0
+        if not fits:
+            raise MgenxError(f"pcap2mgen: the TCP streams need {st.scratch_bytes} bytes of "
+                             f"scratch, the buffer has {buf.numel() - tcp_at}")
+        recs, _, k = eng.tcp_frame(buf, streams, int(st.n_streams), piece_end, piece_pkt,
+                                   int(st.n_pieces), p["rx_sec"], p["rx_usec"])
+        self.last_tcp_records = k
+        return (recs, k) if k else None
 
     def _per_flow(self, p, flow_idx, n, n_flows) -> int:
         """Report slots per flow: a window closes at most once per record and at most once
@@ -218,12 +273,12 @@ class Pcap2Mgen:
 
 
 def pcap2mgen(file, analytics=False, log_rx=True, window=1.0, epoch=False, device=0,
-              reassemble=False, frag_timeout=30.0) -> bytes:
+              reassemble=False, frag_timeout=30.0, tcp=False) -> bytes:
     """One-shot helper: the log text of a pcap or pcapng file image."""
     eng = Engine(device)
     try:
-        return Pcap2Mgen(eng, analytics, log_rx, window, epoch, reassemble,
-                         frag_timeout).run(file)
+        return Pcap2Mgen(eng, analytics, log_rx, window, epoch, reassemble, frag_timeout,
+                         tcp).run(file)
     finally:
         eng.close()
 

@@ -12,7 +12,9 @@
 // rebuilds fragmented IPv4 / IPv6 datagrams (the reference skips their fragments) and
 // "fragtime <sec>" sets how long a datagram may take to complete (default 30, 0 = no limit).
 // The two are matched after the commands above, so every prefix that named one of those
-// ("re" is report, "f" is flush) still does.
+// ("re" is report, "f" is flush) still does.  "tcp" logs the MGEN messages of TCP connections
+// (the reference drops every packet that is not UDP); it is matched after all of those, so
+// "t" is still trace.
 #include <ctype.h>
 #include <stdio.h>
 #include <string.h>
@@ -28,6 +30,7 @@ enum CmdType { CMD_INVALID, CMD_ARG, CMD_NOARG };
 const char* const kCmds[] = {"-report", "-analytic", "+infile", "+outfile", "-trace",
                              "+rxlog",  "-flush",    "+window", "-epoch",   nullptr};
 const char* const kDefragCmds[] = {"-reassemble", "+fragtime", nullptr};
+const char* const kTcpCmds[] = {"-tcp", nullptr};
 
 // GetCmdType (:71-109): a unique case-insensitive prefix match, in one table
 CmdType MatchCmd(const char* const* table, const std::string& low, const char** which,
@@ -51,7 +54,9 @@ CmdType GetCmdType(const char* cmd, const char** which) {
   bool matched = false;
   const CmdType type = MatchCmd(kCmds, low, which, &matched);
   if (matched) return type;
-  return MatchCmd(kDefragCmds, low, which, &matched);
+  const CmdType defrag = MatchCmd(kDefragCmds, low, which, &matched);
+  if (matched) return defrag;
+  return MatchCmd(kTcpCmds, low, which, &matched);
 }
 
 bool ReadAll(FILE* f, std::vector<uint8_t>& out) {
@@ -120,6 +125,8 @@ int main(int argc, char* argv[]) {
         return -1;
       }
       opt.frag_timeout = v;
+    } else if (!strcmp(which, "tcp")) {
+      opt.tcp = true;
     }  // flush: nothing to do
     i += (t == CMD_ARG) ? 2 : 1;
   }
@@ -139,6 +146,14 @@ int main(int argc, char* argv[]) {
               "%llu incomplete\n",
               (unsigned long long)ds.n_fragments, (unsigned long long)ds.n_datagrams,
               (unsigned long long)ds.n_not_udp, (unsigned long long)ds.n_incomplete);
+    const mgenx_tcp_stats& ts = p.tcp_stats();
+    if (opt.tcp && (ts.n_gap_streams > 0 || ts.n_stale > 0))
+      fprintf(stderr,
+              "pcap2mgen: tcp: %llu streams, %llu records, %llu cut at a gap (%llu bytes "
+              "dropped), %llu stale segments\n",
+              (unsigned long long)ts.n_streams, (unsigned long long)p.tcp_records(),
+              (unsigned long long)ts.n_gap_streams, (unsigned long long)ts.dropped_bytes,
+              (unsigned long long)ts.n_stale);
     if (!log.empty() && fwrite(log.data(), 1, log.size(), outfile) != log.size()) {
       perror("pcap2mgen: write error");
       return -1;
