@@ -11,7 +11,7 @@
  * scratch grow it (hipMalloc) the first time a larger batch arrives -- warm them up with
  * the largest batch before capturing a graph.  The log / report / walk formatters keep
  * one workspace per stream; the stream scans, mgenx_flow_reduce, mgenx_flow_dist,
- * mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per context, so those run on one stream
+ * mgenx_flow_series, mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per context, so those run on one stream
  * at a time per context (one context per concurrent stream).
  *
  * Return value: 0 = launched, <0 = argument/launch error (MGENX_E*).  Per-record
@@ -34,6 +34,8 @@
  *   mgenx_flow_lookup   <- MgenAnalyticTable::FindFlow  include/mgenAnalytic.h:387
  *   mgenx_flow_dist     no reference code: the latency distribution, jitter and re-ordering
  *                       the manual reads logs for (doc/mgen.xml:3399-3450)
+ *   mgenx_flow_series   no reference code: rate, loss, latency and jitter per flow and window
+ *                       of receive time, what the manual plots with trpr (doc/mgen.xml:3452-3457)
  */
 #ifndef MGENX_H
 #define MGENX_H
@@ -658,6 +660,61 @@ int mgenx_flow_dist_quantiles(mgenx_ctx* ctx, const struct mgenx_flow_dist* dev_
                               void* stream);
 uint32_t mgenx_flow_dist_bin(uint64_t v);
 uint64_t mgenx_flow_dist_bin_lo(uint32_t bin);
+
+/* ---- per-flow time series: windowed rate, loss, latency and jitter ----
+ * What a receiver log is plotted as (doc/mgen.xml:3452-3457 sends the user to trpr for it):
+ * per flow and per window of receive time, on one time axis for all flows, how much arrived,
+ * how the sequence numbers moved and what the latency did.  No reference code: the definition
+ * below is the contract.  Integer arithmetic; the result is the bytes a serial walk of the
+ * records leaves, whatever order the workgroups finish in.
+ *
+ * Records i < n with dev_flow_idx[i] < n_flows count, in receive order (others are skipped,
+ * MGENX_FLOW_NONE included); rx and lat are mgenx_flow_dist's, signed 64-bit microseconds.
+ * Sequence numbers compare as plain unsigned 32-bit values (a wrap is not followed).
+ * For record k of a flow:
+ *   M   the largest seq among the flow's earlier records, earlier calls included (the flow's
+ *       first record has none)
+ *   b   floor((rx - t0_us) / width_us), a signed floor: rx < t0_us gives b < 0
+ * A record whose b lies outside [0, n_bins) adds 1 to state.outside and to no bin; it still
+ * counts in state.n, still moves M, and is still the predecessor of the next record's jitter.
+ * Otherwise dev_bins[f * n_bins + b] takes
+ *   n += 1, bytes += msg_len, lat_sum / lat_min / lat_max from lat
+ *   jitter_sum += abs(lat - lat_prev)   when the flow has an earlier record (any bin, any call)
+ *   the flow's first record:  fresh += 1, advance += 1
+ *   seq > M:                  fresh += 1, advance += seq - M
+ *   seq < M:                  late += 1
+ *   seq == M:                 neither
+ * Reading the sequence terms: advance is how many sequence numbers the window moved past,
+ * advance - fresh the number skipped in that window (the loss as seen then), late the number
+ * of records that arrived after being skipped (loss taken back).  Over a flow whose records
+ * all fall inside bins, the sum of advance is seq_max - (the first record's seq) + 1.
+ * Streaming: calls over consecutive batches with the same t0_us, width_us and n_bins leave
+ * the bytes one call over the concatenation leaves.  n == 0 or n_flows == 0 touches nothing.
+ * MGENX_EINVAL: width_us == 0, n_bins == 0, a null required pointer, n_flows * n_bins >= 2^31.
+ * Synchronous on `stream` only when the workspace must grow. */
+struct mgenx_flow_series_bin {       /* 64 B; one per (flow, time bin) */
+  uint64_t n, bytes;                 /* records; sum of msg_len */
+  int64_t  lat_sum, lat_min, lat_max;/* INT64_MAX / INT64_MIN while n == 0; the sum wraps */
+  uint64_t jitter_sum;               /* sum of |lat_k - lat_{k-1}| credited to record k's bin */
+  uint64_t advance;
+  uint32_t fresh, late;              /* counts, modulo 2^32 */
+};
+struct mgenx_flow_series_state {     /* 32 B; per flow, carried between calls */
+  uint64_t n;                        /* records counted so far, inside a bin or not */
+  int64_t  last_lat;
+  uint64_t outside;                  /* records whose bin index fell outside [0, n_bins) */
+  uint32_t seq_max, rsv;
+};
+int mgenx_flow_series_init(mgenx_ctx* ctx, struct mgenx_flow_series_state* dev_state,
+                           struct mgenx_flow_series_bin* dev_bins, uint32_t n_flows,
+                           uint32_t n_bins, void* stream);
+/* dev_bins: [n_flows * n_bins], row f = flow f */
+int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_seq,
+                      const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                      const uint16_t* dev_msg_len, const uint32_t* dev_rx_sec,
+                      const uint32_t* dev_rx_usec, uint32_t n, int64_t t0_us, uint64_t width_us,
+                      uint32_t n_bins, struct mgenx_flow_series_state* dev_state,
+                      struct mgenx_flow_series_bin* dev_bins, uint32_t n_flows, void* stream);
 
 
 /* ---- MgenAnalyticTable::FindFlow for batches (mgenAnalytic.cpp:312-328) ----

@@ -13,6 +13,9 @@
 //                  (src, dst, flow id) -> MgenAnalytic::Update per record, reports out;
 //   FlowDistribution  the delivery statistics a log is read for (latency histogram and
 //                  quantiles, jitter, receive gaps, reordering): mgenx_flow_dist per batch;
+//   FlowSeries     the same log as a time series (records, bytes, latency, jitter and the
+//                  movement of the sequence numbers per flow and window of receive time, all
+//                  flows on one time axis): mgenx_flow_series per batch;
 //   ShardedScan    MgenTcpTransport / MgenAppSinkTransport framing (mgenTransport.cpp:
 //                  1683-1760, mgenAppSinkTransport.cpp:369-434) of ONE stream split over the
 //                  ranks of a job (the stitch protocol of include/mgenx.h, "sharded framing",
@@ -655,6 +658,66 @@ class FlowDistribution {
   DeviceArray<State> dist_;
   DeviceArray<uint64_t> hist_;
   DeviceArray<int64_t> d_q_;
+  DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
+};
+
+// ---- per-flow time series: windowed rate, loss, latency and jitter -------------------------
+// mgenx_flow_series over batches (include/mgenx.h): window b of every flow covers the receive
+// times [t0_us + b * width_us, t0_us + (b + 1) * width_us); state and bins kept on the device
+// across Update calls.  Flow indices as FlowAnalytics::FindFlow gives them.
+class FlowSeries {
+ public:
+  typedef struct mgenx_flow_series_state State;
+  typedef struct mgenx_flow_series_bin Bin;
+  FlowSeries(Context& ctx, uint32_t maxFlows, int64_t t0_us, uint64_t width_us, uint32_t nBins)
+      : ctx_(ctx), max_(maxFlows), t0_(t0_us), width_(width_us), bins_n_(nBins),
+        state_(maxFlows), bins_((size_t)maxFlows * nBins) {
+    ctx_.Check(mgenx_flow_series_init(ctx_.get(), state_.data(), bins_.data(), maxFlows, nBins,
+                                      ctx_.stream()), "mgenx_flow_series_init");
+  }
+  // Every record of a decoded batch, in receive order (FlowAnalytics::Update's arguments).
+  void Update(const RecvBatch& b, const std::vector<uint32_t>& flowIdx,
+              const std::vector<uint32_t>& rxSec, const std::vector<uint32_t>& rxUsec) {
+    const uint32_t n = b.Size();
+    d_idx_.Resize(n);
+    d_rxs_.Resize(n);
+    d_rxu_.Resize(n);
+    hipStream_t s = ctx_.stream();
+    check_hip(hipMemcpyAsync(d_idx_.data(), flowIdx.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxs_.data(), rxSec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxu_.data(), rxUsec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    ctx_.Check(mgenx_flow_series(ctx_.get(), d_idx_.data(), b.DevSeq(), b.DevTxSec(),
+                                 b.DevTxUsec(), b.DevMsgLen(), d_rxs_.data(), d_rxu_.data(), n,
+                                 t0_, width_, bins_n_, state_.data(), bins_.data(), max_, s),
+               "mgenx_flow_series");
+    ctx_.Sync();  // the host vectors are the caller's again
+  }
+  // the per-flow carry so far (records counted, records outside the bins, seq_max)
+  std::vector<State> States() { return Download(state_, max_); }
+  // [flow * NumBins() + bin]
+  std::vector<Bin> Bins() { return Download(bins_, (size_t)max_ * bins_n_); }
+  uint32_t NumBins() const { return bins_n_; }
+  int64_t BinStart(uint32_t bin) const { return t0_ + (int64_t)(bin * width_); }
+  State* DevStates() const { return state_.data(); }
+  Bin* DevBins() const { return bins_.data(); }
+
+ private:
+  template <typename T>
+  std::vector<T> Download(const DeviceArray<T>& d, size_t n) {
+    std::vector<T> out(n);
+    if (n)
+      check_hip(hipMemcpyAsync(out.data(), d.data(), n * sizeof(T), hipMemcpyDeviceToHost,
+                               ctx_.stream()), "D2H");
+    ctx_.Sync();
+    return out;
+  }
+  Context& ctx_;
+  uint32_t max_;
+  int64_t t0_;
+  uint64_t width_;
+  uint32_t bins_n_;
+  DeviceArray<State> state_;
+  DeviceArray<Bin> bins_;
   DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
 };
 

@@ -28,7 +28,7 @@ from ._abi import (  # noqa: F401
     PARSE_NO_DAYS, LOGPARSE_COLS, LogparseOut,
     PCAP_NG, PcapngInfo, PCAPNG_IF_DTYPE, PCAPNG_OK, PCAPNG_TRUNCATED, PCAPNG_BLOCK,
     PCAPNG_SECTION, PCAPNG_LINKTYPE, PCAPNG_NO_IFACE, PCAPNG_TSRESOL, PCAPNG_CAPLEN,
-    FLOW_DIST_BINS, FLOW_DIST_DTYPE,
+    FLOW_DIST_BINS, FLOW_DIST_DTYPE, FLOW_SERIES_BIN_DTYPE, FLOW_SERIES_STATE_DTYPE,
     ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
     PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
 )
@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcapng_index", "mgenx_pcapng_parse", "mgenx_pcapng_snap",
     "mgenx_flow_dist_init", "mgenx_flow_dist", "mgenx_flow_dist_quantiles",
     "mgenx_flow_dist_bin", "mgenx_flow_dist_bin_lo",
+    "mgenx_flow_series_init", "mgenx_flow_series",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
 )
@@ -166,6 +167,9 @@ def load(diag: bool = False):
     L.mgenx_flow_dist_init.argtypes = [P, P, P, u32, P]
     L.mgenx_flow_dist.argtypes = [P, P, P, P, P, P, P, P, u32, P, P, u32, P]
     L.mgenx_flow_dist_quantiles.argtypes = [P, P, P, u32, ctypes.POINTER(u32), u32, P, P]
+    L.mgenx_flow_series_init.argtypes = [P, P, P, u32, u32, P]
+    L.mgenx_flow_series.argtypes = [P, P, P, P, P, P, P, P, u32, ctypes.c_int64, u64, u32, P, P,
+                                    u32, P]
     L.mgenx_flow_dist_bin.argtypes = [u64]
     L.mgenx_flow_dist_bin.restype = u32
     L.mgenx_flow_dist_bin_lo.argtypes = [u32]
@@ -648,6 +652,33 @@ class Engine:
                                                        _stream(self.device)),
                     "mgenx_flow_dist_quantiles")
         return out
+
+    def flow_series_init(self, n_flows, n_bins):
+        """Fresh per-flow time series (mgenx_flow_series_init): (state, bins), uint8 tensors of
+        n_flows x 32 B (FLOW_SERIES_STATE_DTYPE) and n_flows x n_bins x 64 B
+        (FLOW_SERIES_BIN_DTYPE, row f = flow f)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        state = torch.empty(n_flows * FLOW_SERIES_STATE_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        bins = torch.empty(n_flows * n_bins * FLOW_SERIES_BIN_DTYPE.itemsize, dtype=torch.uint8,
+                           device=dev)
+        self._check(self.lib.mgenx_flow_series_init(self.ctx, _ptr(state), _ptr(bins), n_flows,
+                                                    n_bins, _stream(self.device)),
+                    "mgenx_flow_series_init")
+        return state, bins
+
+    def flow_series(self, state, bins, n_flows, n_bins, t0_us, width_us, flow_idx, seq, tx_sec,
+                    tx_usec, msg_len, rx_sec, rx_usec, n=None):
+        """Records in receive order added to the bins floor((rx - t0_us) / width_us) of their
+        flows (mgenx_flow_series); batches may follow each other with the same t0_us, width_us
+        and n_bins."""
+        n = flow_idx.numel() if n is None else n
+        self._check(self.lib.mgenx_flow_series(self.ctx, _ptr(flow_idx), _ptr(seq), _ptr(tx_sec),
+                                               _ptr(tx_usec), _ptr(msg_len), _ptr(rx_sec),
+                                               _ptr(rx_usec), n, int(t0_us), int(width_us),
+                                               int(n_bins), _ptr(state), _ptr(bins), n_flows,
+                                               _stream(self.device)), "mgenx_flow_series")
 
     def flow_keys(self, table, n_flows, protocol=1, keys=None):
         """The report_msg key of every flow index < n_flows (mgenx_flow_keys): a uint8
@@ -1208,6 +1239,61 @@ def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
         return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
                 dist.cpu().numpy().view(FLOW_DIST_DTYPE)[:nf].copy(), quant.cpu().numpy(),
                 hist.cpu().numpy().view(np.uint64), n, n_bad)
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
+        eng.close()
+
+
+def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_base=0,
+                            device=0) -> tuple:
+    """Per-flow time series of an MGEN text log, on the GPU: line index -> parse -> FindFlow ->
+    mgenx_flow_series.  Returns (keys, state, bins, t0_us, n_lines, n_malformed): numpy arrays
+    of REPORT_KEY_DTYPE, FLOW_SERIES_STATE_DTYPE and FLOW_SERIES_BIN_DTYPE [n_flows, n_bins],
+    flows in analyze_text_log's order.  By default t0_us is the lowest receive time among the
+    counted records and n_bins just enough to hold the highest (mgenx_flow_span)."""
+    import torch
+    width_us = int(width_us)
+    if width_us < 1:
+        raise ValueError("width_us must be at least 1")
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
+        line_off, n = eng.text_index(text)
+
+        def empty(n_lines, n_bad):
+            return (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_SERIES_STATE_DTYPE),
+                    np.zeros((0, n_bins or 1), FLOW_SERIES_BIN_DTYPE),
+                    0 if t0_us is None else int(t0_us), n_lines, n_bad)
+        if n == 0:
+            return empty(0, 0)
+        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+        n_bad = int((p["status"] != PARSE_OK).sum().item())
+        table = eng.flow_table(max(n, 16))
+        flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
+        nf = int(n_flows.item())
+        if nf == 0:
+            return empty(n, n_bad)
+        if t0_us is None or n_bins is None:
+            _, lo, hi = eng.flow_span(flow_idx, p["rx_sec"], p["rx_usec"], n, nf)
+            if t0_us is None:
+                t0_us = lo
+            if n_bins is None:
+                n_bins = max((hi - int(t0_us)) // width_us + 1, 1)
+        t0_us, n_bins = int(t0_us), int(n_bins)
+        state, bins = eng.flow_series_init(nf, n_bins)
+        eng.flow_series(state, bins, nf, n_bins, t0_us, width_us, flow_idx, p["seq_num"],
+                        p["tx_sec"], p["tx_usec"], p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+        recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
+        proto = int(p["protocol"][recv][0].item())
+        keys = eng.flow_keys(table, nf, protocol=proto)
+        torch.cuda.synchronize(device)
+        return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
+                state.cpu().numpy().view(FLOW_SERIES_STATE_DTYPE).copy(),
+                bins.cpu().numpy().view(FLOW_SERIES_BIN_DTYPE).reshape(nf, n_bins).copy(),
+                t0_us, n, n_bad)
     finally:
         if table is not None:
             eng.flow_table_destroy(table)

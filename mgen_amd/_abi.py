@@ -150,6 +150,14 @@ FLOW_DIST_DTYPE = np.dtype([
     ("first_rx", "<i8"), ("last_rx", "<i8"), ("last_lat", "<i8"), ("rsv", "<u8", (2,))])
 assert FLOW_DIST_DTYPE.itemsize == 160
 
+# ---- per-flow time series (mgenx_flow_series, include/mgenx.h) ----
+FLOW_SERIES_BIN_DTYPE = np.dtype([
+    ("n", "<u8"), ("bytes", "<u8"), ("lat_sum", "<i8"), ("lat_min", "<i8"), ("lat_max", "<i8"),
+    ("jitter_sum", "<u8"), ("advance", "<u8"), ("fresh", "<u4"), ("late", "<u4")])
+FLOW_SERIES_STATE_DTYPE = np.dtype([
+    ("n", "<u8"), ("last_lat", "<i8"), ("outside", "<u8"), ("seq_max", "<u4"), ("rsv", "<u4")])
+assert FLOW_SERIES_BIN_DTYPE.itemsize == 64 and FLOW_SERIES_STATE_DTYPE.itemsize == 32
+
 
 # ---- pcap2mgen / text interleave (include/mgenx.h) ----
 class PcapInfo(ctypes.Structure):      # mgenx_pcap_info

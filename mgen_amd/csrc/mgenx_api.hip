@@ -157,6 +157,18 @@ extern "C" int mgenx_flow_dist_run(void* ws, const uint32_t* flow_idx, const uin
                                    const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
                                    struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
                                    hipStream_t stream, char* err, size_t errn);
+extern "C" void* mgenx_flowseries_ws_new();
+extern "C" void mgenx_flowseries_ws_free(void* p);
+extern "C" int mgenx_flow_series_init_run(struct mgenx_flow_series_state* state,
+                                          struct mgenx_flow_series_bin* bins, uint32_t n_flows,
+                                          uint32_t n_bins, hipStream_t stream);
+extern "C" int mgenx_flow_series_run(void* ws, const uint32_t* flow_idx, const uint32_t* seq,
+                                     const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                                     const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                                     int64_t t0, uint64_t width, uint32_t n_bins,
+                                     struct mgenx_flow_series_state* state,
+                                     struct mgenx_flow_series_bin* bins, uint32_t n_flows,
+                                     hipStream_t stream, char* err, size_t errn);
 extern "C" int mgenx_flow_dist_quantiles_run(const struct mgenx_flow_dist* dist,
                                              const uint64_t* hist, uint32_t n_flows,
                                              const uint32_t* permille, uint32_t n_q, int64_t* out,
@@ -222,6 +234,7 @@ struct mgenx_ctx {
   void* scan_ws = nullptr;        // stream-scan workspace (mgenx_scan.hip), grown on demand
   void* flow_ws = nullptr;        // flow-reduce workspace (mgenx_analytic.hip), grown on demand
   void* flowdist_ws = nullptr;    // flow-dist workspace (mgenx_flowdist.hip), grown on demand
+  void* flowseries_ws = nullptr;  // flow-series workspace (mgenx_flowseries.hip), grown on demand
   void* log_ws = nullptr;         // log-format workspace (mgenx_log.hip), grown on demand
   void* tcp_ws = nullptr;         // TCP transmit workspace (mgenx_pack_tcp), grown on demand
   size_t tcp_ws_bytes = 0;
@@ -428,6 +441,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   if (c->scan_ws) mgenx_scan_ws_free(c->scan_ws);
   if (c->flow_ws) mgenx_flow_ws_free(c->flow_ws);
   if (c->flowdist_ws) mgenx_flowdist_ws_free(c->flowdist_ws);
+  if (c->flowseries_ws) mgenx_flowseries_ws_free(c->flowseries_ws);
   if (c->log_ws) mgenx_log_ws_free(c->log_ws);
   mgenx::dev_free(c->tcp_ws);
   mgenx::dev_free(c->tcp_plan);
@@ -987,6 +1001,36 @@ int mgenx_flow_dist_quantiles(mgenx_ctx* ctx, const struct mgenx_flow_dist* dev_
 
 uint32_t mgenx_flow_dist_bin(uint64_t v) { return mgenx::flow_dist_bin(v); }
 uint64_t mgenx_flow_dist_bin_lo(uint32_t bin) { return mgenx::flow_dist_bin_lo(bin); }
+
+int mgenx_flow_series_init(mgenx_ctx* ctx, struct mgenx_flow_series_state* dev_state,
+                           struct mgenx_flow_series_bin* dev_bins, uint32_t n_flows,
+                           uint32_t n_bins, void* stream) {
+  if (!ctx || n_bins == 0 || (uint64_t)n_flows * n_bins >= (1ull << 31)) return MGENX_EINVAL;
+  if (n_flows == 0) return MGENX_OK;
+  if (!dev_state || !dev_bins) return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return mgenx_flow_series_init_run(dev_state, dev_bins, n_flows, n_bins, (hipStream_t)stream);
+}
+
+int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_seq,
+                      const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                      const uint16_t* dev_msg_len, const uint32_t* dev_rx_sec,
+                      const uint32_t* dev_rx_usec, uint32_t n, int64_t t0_us, uint64_t width_us,
+                      uint32_t n_bins, struct mgenx_flow_series_state* dev_state,
+                      struct mgenx_flow_series_bin* dev_bins, uint32_t n_flows, void* stream) {
+  if (!ctx || width_us == 0 || n_bins == 0 || (uint64_t)n_flows * n_bins >= (1ull << 31))
+    return MGENX_EINVAL;
+  if (n == 0 || n_flows == 0) return MGENX_OK;
+  if (!dev_flow_idx || !dev_seq || !dev_tx_sec || !dev_tx_usec || !dev_msg_len || !dev_rx_sec ||
+      !dev_rx_usec || !dev_state || !dev_bins || n > 0x7FFFFFFFu)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (!ctx->flowseries_ws) ctx->flowseries_ws = mgenx_flowseries_ws_new();
+  return mgenx_flow_series_run(ctx->flowseries_ws, dev_flow_idx, dev_seq, dev_tx_sec, dev_tx_usec,
+                               dev_msg_len, dev_rx_sec, dev_rx_usec, n, t0_us, width_us, n_bins,
+                               dev_state, dev_bins, n_flows, (hipStream_t)stream, ctx->err,
+                               sizeof(ctx->err));
+}
 
 static int log_recv(mgenx_ctx* ctx, bool binary, const uint8_t* dev_slab, uint64_t slab_bytes,
                     const uint64_t* dev_rec_off, const uint32_t* dev_rec_len, uint64_t stride,

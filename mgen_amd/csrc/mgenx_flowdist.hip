@@ -21,6 +21,8 @@
 //      histogram and a workgroup reduction flushed with one atomic per field and non-zero bin,
 //      or (shorter runs) atomics straight from the lanes.  Sums, minima and maxima of integers
 //      commute, so the bytes left do not depend on the order the workgroups finish in.
+// Passes 1 and 2 are mgenx_flow_prep_run, which mgenx_flow_series (mgenx_flowseries.hip) runs too;
+// what both main passes use of them (DistRec, block_segmax, kChunk) is in mgenx_flowdist.hpp.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
@@ -35,11 +37,8 @@ namespace mgenx {
 typedef struct mgenx_flow_dist DistState;
 static_assert(sizeof(DistState) == 160, "mgenx_flow_dist is 160 B");
 
-constexpr uint32_t kChunk = 1024;   // sorted positions (= lanes) per workgroup
-constexpr uint32_t kWaves = kChunk / 64;
 constexpr uint32_t kLong = 128;     // a run of this many lanes takes the LDS path
 constexpr uint32_t kMaxLong = kChunk / kLong;
-constexpr int64_t kNone = -1;       // "no earlier record" as a running maximum of u32 values
 
 // what a flow's first record of the batch pairs with
 struct DistSnap {
@@ -94,56 +93,6 @@ __device__ __forceinline__ void field_flush(DistState* d, int k, int64_t v) {
   }
 }
 
-// ---- segmented inclusive max scan over the kChunk lanes of a workgroup ----
-// `head` starts a segment at this lane.  Returns the maximum of v over the lanes from the
-// lane's segment start (or lane 0) to the lane; *open = no segment starts at or before it.
-// s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
-__device__ __forceinline__ int64_t block_segmax(int64_t v, bool head, int64_t* s_v, uint32_t* s_h,
-                                                bool* open) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const int64_t pv = __shfl_up((long long)v, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      v = v > pv ? v : pv;
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_v[w] = v;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    int64_t wv = lane < kWaves ? s_v[lane] : kNone;
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const int64_t pv = __shfl_up((long long)wv, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        wv = wv > pv ? wv : pv;
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) {
-      s_v[lane] = wv;
-      s_h[lane] = wh;
-    }
-  }
-  __syncthreads();
-  if (w > 0 && !h) {
-    const int64_t pv = s_v[w - 1];
-    v = v > pv ? v : pv;
-    h = s_h[w - 1];
-  }
-  *open = h == 0u;
-  __syncthreads();
-  return v;
-}
-
 __global__ void flow_dist_init_kernel(DistState* dist, uint32_t n_flows) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_flows) return;
@@ -168,16 +117,6 @@ __global__ void flow_dist_snap_kernel(const DistState* __restrict__ dist, uint32
   s.rsv = 0;
   snap[f] = s;
 }
-
-// One record as the passes read it: the sorted order puts a flow's consecutive records about
-// n_flows records apart, so a lane gathering six columns touches six cache lines for 22 bytes.
-// flow_dist_pack_kernel reads the columns once, coalesced, and leaves one 32-B record per input
-// record (latency and receive time already in microseconds): one gather per lane instead of six.
-struct alignas(16) DistRec {
-  int64_t lat, rx;
-  uint32_t seq, len, rsv0, rsv1;
-};
-static_assert(sizeof(DistRec) == 32, "DistRec is 32 B");
 
 struct DistCols {
   const uint32_t *seq, *txs, *txu;
@@ -540,6 +479,44 @@ extern "C" int mgenx_flow_dist_init_run(DistState* dist, uint64_t* hist, uint32_
 
 static size_t fd_a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// the passes mgenx_flow_dist and mgenx_flow_series share (mgenx_flowdist.hpp)
+extern "C" size_t mgenx_flow_prep_ws(uint32_t n, uint32_t n_flows) {
+  const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
+  return fd_a256(mgenx_flow_sort_ws(n, n_flows)) + 2 * fd_a256((size_t)n_chunks * 8u) +
+         fd_a256((size_t)n_chunks * 4u) + fd_a256((size_t)n * sizeof(DistRec));
+}
+
+extern "C" int mgenx_flow_prep_run(void* mem, const uint32_t* flow_idx, const uint32_t* seq,
+                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
+                                   const uint32_t** bnd, const DistRec** rec_out,
+                                   const int64_t** scan_out, hipStream_t stream, char* err,
+                                   size_t errn) {
+  const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
+  const size_t c8 = fd_a256((size_t)n_chunks * 8u), c4 = fd_a256((size_t)n_chunks * 4u);
+  char* p = static_cast<char*>(mem);
+  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  void* sort_mem = take(fd_a256(mgenx_flow_sort_ws(n, n_flows)));
+  int64_t* tail_max = (int64_t*)take(c8);
+  int64_t* scan = (int64_t*)take(c8);
+  uint32_t* tail_cont = (uint32_t*)take(c4);
+  DistRec* rec = (DistRec*)take(fd_a256((size_t)n * sizeof(DistRec)));
+  const int rc = mgenx_flow_sort_run(sort_mem, flow_idx, n, n_flows, keys, order, bnd, stream, err,
+                                     errn);
+  if (rc != MGENX_OK) return rc;
+  const DistCols col = {seq, txs, txu, len, rxs, rxu};
+  hipLaunchKernelGGL(flow_dist_pack_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, col, n,
+                     rec);
+  hipLaunchKernelGGL(flow_dist_tail_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, *keys, *order,
+                     *bnd, n_flows, seq, tail_max, tail_cont);
+  hipLaunchKernelGGL(flow_dist_carry_kernel, dim3(1), dim3(kChunk), 0, stream, tail_max, tail_cont,
+                     n_chunks, scan);
+  *rec_out = rec;
+  *scan_out = scan;
+  return MGENX_OK;
+}
+
 extern "C" int mgenx_flow_dist_run(void* wsp, const uint32_t* flow_idx, const uint32_t* seq,
                                    const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
                                    const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
@@ -548,11 +525,8 @@ extern "C" int mgenx_flow_dist_run(void* wsp, const uint32_t* flow_idx, const ui
   mgenx_flowdist_ws& ws = *static_cast<mgenx_flowdist_ws*>(wsp);
   if (n == 0 || n_flows == 0) return MGENX_OK;
   const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
-  const size_t sort_b = fd_a256(mgenx_flow_sort_ws(n, n_flows));
   const size_t snap_b = fd_a256((size_t)n_flows * sizeof(DistSnap));
-  const size_t c8 = fd_a256((size_t)n_chunks * 8u), c4 = fd_a256((size_t)n_chunks * 4u);
-  const size_t rec_b = fd_a256((size_t)n * sizeof(DistRec));
-  const size_t need = sort_b + snap_b + 2 * c8 + c4 + rec_b;
+  const size_t need = snap_b + mgenx_flow_prep_ws(n, n_flows);
   if (ws.bytes < need) {
     mgenx::dev_free(ws.mem);
     ws.mem = nullptr;
@@ -563,28 +537,16 @@ extern "C" int mgenx_flow_dist_run(void* wsp, const uint32_t* flow_idx, const ui
     }
     ws.bytes = need;
   }
-  char* p = static_cast<char*>(ws.mem);
-  auto take = [&](size_t b) { char* q = p; p += b; return q; };
-  void* sort_mem = take(sort_b);
-  DistSnap* snap = (DistSnap*)take(snap_b);
-  int64_t* tail_max = (int64_t*)take(c8);
-  int64_t* scan = (int64_t*)take(c8);
-  uint32_t* tail_cont = (uint32_t*)take(c4);
-  DistRec* rec = (DistRec*)take(rec_b);
-
+  DistSnap* snap = (DistSnap*)ws.mem;
   hipLaunchKernelGGL(flow_dist_snap_kernel, dim3((n_flows + 255u) / 256u), dim3(256), 0, stream,
                      dist, n_flows, snap);
   const uint32_t *keys, *order, *bnd;
-  const int rc = mgenx_flow_sort_run(sort_mem, flow_idx, n, n_flows, &keys, &order, &bnd, stream,
-                                     err, errn);
+  const DistRec* rec;
+  const int64_t* scan;
+  const int rc = mgenx_flow_prep_run(static_cast<char*>(ws.mem) + snap_b, flow_idx, seq, txs, txu,
+                                     len, rxs, rxu, n, n_flows, &keys, &order, &bnd, &rec, &scan,
+                                     stream, err, errn);
   if (rc != MGENX_OK) return rc;
-  const DistCols col = {seq, txs, txu, len, rxs, rxu};
-  hipLaunchKernelGGL(flow_dist_pack_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, col, n,
-                     rec);
-  hipLaunchKernelGGL(flow_dist_tail_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, order,
-                     bnd, n_flows, seq, tail_max, tail_cont);
-  hipLaunchKernelGGL(flow_dist_carry_kernel, dim3(1), dim3(kChunk), 0, stream, tail_max, tail_cont,
-                     n_chunks, scan);
   if (hist)
     hipLaunchKernelGGL(flow_dist_main_kernel<true>, dim3(n_chunks), dim3(kChunk), 0, stream, keys,
                        order, bnd, n_flows, rec, snap, scan, dist, hist);

@@ -1,5 +1,7 @@
 // The latency histogram's bin arithmetic (mgenx_flow_dist): one definition for the kernels and
-// the exported host functions mgenx_flow_dist_bin / mgenx_flow_dist_bin_lo.
+// the exported host functions mgenx_flow_dist_bin / mgenx_flow_dist_bin_lo.  Below it, what
+// mgenx_flow_dist and mgenx_flow_series share: the chunk size, the packed record, the segmented
+// max scan and the sort / pack / carry passes behind mgenx_flow_prep_run.
 //
 // 0 <= v < 2^32 microseconds in MGENX_FLOW_DIST_BINS = 896 bins: one bin per value below 64, then
 // 32 sub-bins per octave (a relative width of 1/32 .. 1/64):
@@ -13,6 +15,7 @@
 #include "mgenx.h"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define MGENX_HD __host__ __device__
 #else
 #define MGENX_HD
@@ -36,4 +39,87 @@ MGENX_HD inline uint64_t flow_dist_bin_lo(uint32_t b) {
   return (uint64_t)(32u + k % 32u) << (k / 32u + 1u);
 }
 
+// ---- what the per-flow passes share (mgenx_flowdist.hip, mgenx_flowseries.hip) ----
+constexpr uint32_t kChunk = 1024;   // sorted positions (= lanes) per workgroup
+constexpr uint32_t kWaves = kChunk / 64;
+constexpr int64_t kNone = -1;       // "no earlier record" as a running maximum of u32 values
+
+// One record as the passes read it: the sorted order puts a flow's consecutive records about
+// n_flows records apart, so a lane gathering six columns touches six cache lines for 22 bytes.
+// flow_dist_pack_kernel reads the columns once, coalesced, and leaves one 32-B record per input
+// record (latency and receive time already in microseconds): one gather per lane instead of six.
+struct alignas(16) DistRec {
+  int64_t lat, rx;
+  uint32_t seq, len, rsv0, rsv1;
+};
+static_assert(sizeof(DistRec) == 32, "DistRec is 32 B");
+
+#if defined(__HIPCC__)
+// ---- segmented inclusive max scan over the kChunk lanes of a workgroup ----
+// `head` starts a segment at this lane.  Returns the maximum of v over the lanes from the
+// lane's segment start (or lane 0) to the lane; *open = no segment starts at or before it.
+// s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
+__device__ __forceinline__ int64_t block_segmax(int64_t v, bool head, int64_t* s_v, uint32_t* s_h,
+                                                bool* open) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint32_t h = head ? 1u : 0u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const int64_t pv = __shfl_up((long long)v, d);
+    const uint32_t ph = __shfl_up(h, d);
+    if (lane >= d && !h) {
+      v = v > pv ? v : pv;
+      h = ph;
+    }
+  }
+  if (lane == 63u) {
+    s_v[w] = v;
+    s_h[w] = h;
+  }
+  __syncthreads();
+  if (w == 0) {
+    int64_t wv = lane < kWaves ? s_v[lane] : kNone;
+    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
+#pragma unroll
+    for (uint32_t d = 1; d < kWaves; d <<= 1) {
+      const int64_t pv = __shfl_up((long long)wv, d);
+      const uint32_t ph = __shfl_up(wh, d);
+      if (lane >= d && !wh) {
+        wv = wv > pv ? wv : pv;
+        wh = ph;
+      }
+    }
+    if (lane < kWaves) {
+      s_v[lane] = wv;
+      s_h[lane] = wh;
+    }
+  }
+  __syncthreads();
+  if (w > 0 && !h) {
+    const int64_t pv = s_v[w - 1];
+    v = v > pv ? v : pv;
+    h = s_h[w - 1];
+  }
+  *open = h == 0u;
+  __syncthreads();
+  return v;
+}
+#endif
+
 }  // namespace mgenx
+
+// The passes mgenx_flow_dist and mgenx_flow_series share (mgenx_flowdist.hip): the stable sort
+// by flow (keys / order / bnd as mgenx_flow_sort_run leaves them), the packed records rec[i] of
+// the input order, and scan[c], the largest seq of chunk c's last flow over chunk c and the
+// chunks before it that this flow fills.  mem: mgenx_flow_prep_ws(n, n_flows) bytes of device
+// memory, 256-B aligned; n, n_flows >= 1.
+#if defined(__HIPCC__)
+extern "C" size_t mgenx_flow_prep_ws(uint32_t n, uint32_t n_flows);
+extern "C" int mgenx_flow_prep_run(void* mem, const uint32_t* flow_idx, const uint32_t* seq,
+                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
+                                   const uint32_t** bnd, const mgenx::DistRec** rec,
+                                   const int64_t** scan, hipStream_t stream, char* err,
+                                   size_t errn);
+#endif
