@@ -8,7 +8,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value -Wno
 NAMES := mgenx_api mgenx_unpack mgenx_unpack_fixed mgenx_probe \
          mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_comm mgenx_worker \
          mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse mgenx_flowdist mgenx_defrag \
-         mgenx_pcap_tcp mgenx_flowseries
+         mgenx_pcap_tcp mgenx_flowseries mgenx_match
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
        mgen_amd/csrc/mgenx_unpack_long.hpp mgen_amd/csrc/mgenx_flowsm.hpp \
@@ -22,7 +22,7 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/loopback tests/cpp/compat_shapes tests/cpp/compat_shapes_pl tests/cpp/shim_latency \
      tests/cpp/shard_scan tools/pcap2mgen tests/cpp/logparse_host \
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
-     tests/cpp/flow_series_host
+     tests/cpp/flow_series_host tests/cpp/msg_match_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -99,6 +99,10 @@ tests/cpp/flow_dist_host: tests/cpp/flow_dist_host.cpp include/mgenx.hpp include
 
 # mgenx::FlowSeries over a decoded batch against a serial loop in the program
 tests/cpp/flow_series_host: tests/cpp/flow_series_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
+	$(HOSTCXX) $< -o $@ $(HOSTLD)
+
+# mgenx::MessageMatch over a sender's and a receiver's records against a serial loop in the program
+tests/cpp/msg_match_host: tests/cpp/msg_match_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
 	$(HOSTCXX) $< -o $@ $(HOSTLD)
 
 # mgenx::Pcap2Mgen with PcapOptions::tcp over a capture file (tests/test_gpu_pcap_tcp_cpp.py)

@@ -1322,6 +1322,95 @@ int mgenx_log_parse_text(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
                          const uint64_t* dev_line_off, uint32_t n, uint32_t opts,
                          uint32_t day_base_sec, const mgenx_logparse_out* out, void* stream);
 
+/* ---- a sender's log joined with a receiver's log: per-message loss ----
+ * A sender logging SEND lines (TXLOG) and a receiver logging RECV lines is the manual's basic
+ * workflow.  On the UDP and TCP paths the SEND line carries the message's own tx_time
+ * (mgenTransport.cpp:1060,1392,1805 -> mgenMsg.cpp:1213), which is the RECV line's sent> field,
+ * and flow id, sequence number and destination are on both lines: the join is exact.  No
+ * reference code: the definition below is the contract.  Integer arithmetic only; every output
+ * byte is a function of the inputs alone, whatever the launch geometry and whichever workgroup
+ * finishes first.
+ *
+ * Inputs: two record sets as device columns, with flow indices from one shared numbering:
+ *   send  (ns records, sender-log order):   flow_idx seq t_sec t_usec (the SEND line's stamp)
+ *                                           len (the u32 size)
+ *   recv  (nr records, receiver-log order): flow_idx seq tx_sec tx_usec (sent>) rx_sec rx_usec
+ * A record whose flow_idx >= n_flows (MGENX_FLOW_NONE included) is skipped and counted in
+ * stats.send_skipped / stats.recv_skipped.
+ * Identity of a message: (flow_idx, seq, sec, usec) compared as plain u32 values, from t_* on the
+ * send side and tx_* on the recv side; with MGENX_MATCH_NO_TIME, (flow_idx, seq) only (SINK-sent
+ * logs, whose SEND stamp is the wall clock, mgenAppSinkTransport.cpp:191, and logs whose two
+ * time-stamp styles cannot be reconciled).
+ * Owner: among the counted send records of equal identity the one with the lowest index; the
+ * others are send duplicates.
+ * Per send record i (always written):
+ *   send_rx_count[i]  for an owner the number of counted recv records with its identity; 0 for a
+ *                     send duplicate or a skipped record
+ *   send_first_rx[i]  for an owner the lowest such recv index, else MGENX_MATCH_NONE
+ * Per recv record j: recv_send[j] = its owner's index, or MGENX_MATCH_NONE (skipped or no owner).
+ * Per flow, over the flow's owners in send-log order (an owner is delivered iff its
+ * send_rx_count > 0):
+ *   sent, sent_bytes            owners; sum of their len
+ *   send_dup                    send duplicates
+ *   delivered, delivered_bytes  delivered owners; sum of their len
+ *   rx_dup                      sum of send_rx_count - 1 over delivered owners
+ *   rx_orphan                   counted recv records of this flow with no owner
+ *   lost_head                   undelivered owners before the first delivered one (sent if none
+ *                               was delivered)
+ *   lost_tail                   undelivered owners after the last delivered one (0 if none was)
+ *   loss_runs, loss_run_max     maximal runs of consecutive undelivered owners (send duplicates
+ *                               do not break a run; head and tail runs count); the longest
+ *   loss_run_hist[k]            runs with min(floor(log2(length)), 17) == k
+ *   lat_sum, lat_min, lat_max   over delivered owners, signed 64-bit microseconds
+ *                               (rx_sec - t_sec) * 10^6 + rx_usec - t_usec with the u32 values
+ *                               widened first and rx_* of recv record send_first_rx;
+ *                               INT64_MAX / INT64_MIN while delivered == 0; the sum wraps
+ * sent - delivered is the exact loss; lost_head + lost_tail the part no receiver-only analysis
+ * sees.  Global: send_skipped, recv_skipped, recv_unmatched (counted recv records with no owner:
+ * the sum of rx_orphan) and send_dup (the sum over the flows).
+ *
+ * mgenx_msg_match: asynchronous; every output is fully written (no init call; a flow without
+ * records gets the empty values); ns == 0 and nr == 0 are legal.  One call per pair of logs: it
+ * does not stream across calls.  The context keeps the workspace (at most about 64 bytes per send
+ * record, the stable sort's share included, plus 4 (n_flows + 1)), so the call runs on one
+ * stream at a time per context and synchronises only when the workspace must grow.
+ * MGENX_EINVAL: a null required pointer (the columns of an empty side and, with n_flows == 0,
+ * dev_flows may be null), ns above 2^30, nr or n_flows above 2^31 - 1.
+ *
+ * mgenx_match_side prepares a parsed log (mgenx_log_parse_text) for mgenx_flow_lookup:
+ * dev_err_out[k] = 0 exactly for an MGENX_PARSE_OK line of `want_event` (MGENX_EVENT_SEND or
+ * MGENX_EVENT_RECV), else MGENX_ERROR_NOT_RECV; dev_src_out[k] = the line's src with the address
+ * cleared (type 0, length 0, address bytes 0) and the port kept.  Given as cols.err and dev_src,
+ * a SEND line (which has srcPort only) and the RECV line of the same flow then give
+ * mgenx_flow_lookup the same key: dst addr, dst port, src port, flow id.  Call the lookup once
+ * for the sender log and once for the receiver log on one table, sender first: flows are numbered
+ * by first SEND line, receiver-only flows after them. */
+#define MGENX_MATCH_NONE    0xFFFFFFFFu
+#define MGENX_MATCH_NO_TIME 0x1
+struct mgenx_flow_match {            /* 256 B */
+  uint64_t sent, sent_bytes, send_dup;
+  uint64_t delivered, delivered_bytes, rx_dup, rx_orphan;
+  uint64_t lost_head, lost_tail, loss_runs, loss_run_max;
+  uint64_t loss_run_hist[18];
+  int64_t  lat_sum, lat_min, lat_max;
+};
+struct mgenx_match_stats {           /* 32 B */
+  uint64_t send_skipped, recv_skipped, recv_unmatched, send_dup;
+};
+int mgenx_match_side(mgenx_ctx* ctx, const uint8_t* dev_event, const uint8_t* dev_status,
+                     const mgenx_addr* dev_src, uint32_t n, uint32_t want_event,
+                     mgenx_addr* dev_src_out, uint8_t* dev_err_out, void* stream);
+int mgenx_msg_match(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                    const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                    const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len, uint32_t ns,
+                    const uint32_t* dev_recv_flow_idx, const uint32_t* dev_recv_seq,
+                    const uint32_t* dev_recv_tx_sec, const uint32_t* dev_recv_tx_usec,
+                    const uint32_t* dev_recv_rx_sec, const uint32_t* dev_recv_rx_usec,
+                    uint32_t nr, uint32_t n_flows, uint32_t opts, uint32_t* dev_send_rx_count,
+                    uint32_t* dev_send_first_rx, uint32_t* dev_recv_send,
+                    struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
+                    void* stream);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ----
  * One communicator per rank (one process per GPU): rank 0 calls mgenx_comm_unique_id and
  * hands the MGENX_COMM_ID_BYTES bytes to every rank (any out-of-band channel), then every

@@ -721,6 +721,76 @@ class FlowSeries {
   DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
 };
 
+// ---- a sender's log joined with a receiver's log: per-message loss ---------------------------
+// mgenx_msg_match (include/mgenx.h) over host columns: the sender's records (flow index, seq, the
+// SEND stamp, size) and the receiver's (flow index, seq, sent> stamp, receive time), with flow
+// indices from one numbering.  One Run per pair of logs; the results stay on the device until
+// they are asked for.
+class MessageMatch {
+ public:
+  typedef struct mgenx_flow_match Flow;
+  typedef struct mgenx_match_stats Stats;
+  struct SendColumns {
+    std::vector<uint32_t> flow_idx, seq, t_sec, t_usec, len;
+  };
+  struct RecvColumns {
+    std::vector<uint32_t> flow_idx, seq, tx_sec, tx_usec, rx_sec, rx_usec;
+  };
+  // opts: 0 or MGENX_MATCH_NO_TIME
+  MessageMatch(Context& ctx, uint32_t nFlows, uint32_t opts = 0)
+      : ctx_(ctx), n_flows_(nFlows), opts_(opts), flows_(nFlows), stats_(1) {}
+  void Run(const SendColumns& s, const RecvColumns& r) {
+    ns_ = (uint32_t)s.flow_idx.size();
+    nr_ = (uint32_t)r.flow_idx.size();
+    const std::vector<uint32_t>* sc[5] = {&s.flow_idx, &s.seq, &s.t_sec, &s.t_usec, &s.len};
+    const std::vector<uint32_t>* rc[6] = {&r.flow_idx, &r.seq,    &r.tx_sec,
+                                          &r.tx_usec,  &r.rx_sec, &r.rx_usec};
+    hipStream_t st = ctx_.stream();
+    for (int k = 0; k < 5; k++) Upload(d_s_[k], *sc[k], ns_, st);
+    for (int k = 0; k < 6; k++) Upload(d_r_[k], *rc[k], nr_, st);
+    cnt_.Resize(ns_);
+    first_.Resize(ns_);
+    rs_.Resize(nr_);
+    ctx_.Check(mgenx_msg_match(ctx_.get(), d_s_[0].data(), d_s_[1].data(), d_s_[2].data(),
+                               d_s_[3].data(), d_s_[4].data(), ns_, d_r_[0].data(),
+                               d_r_[1].data(), d_r_[2].data(), d_r_[3].data(), d_r_[4].data(),
+                               d_r_[5].data(), nr_, n_flows_, opts_, cnt_.data(), first_.data(),
+                               rs_.data(), flows_.data(), stats_.data(), st),
+               "mgenx_msg_match");
+    ctx_.Sync();  // the host vectors are the caller's again
+  }
+  std::vector<Flow> Flows() { return Download(flows_, n_flows_); }
+  Stats GetStats() { return Download(stats_, 1)[0]; }
+  // per send record: the recv records with its identity (0 for a duplicate) and the first of them
+  std::vector<uint32_t> SendRxCount() { return Download(cnt_, ns_); }
+  std::vector<uint32_t> SendFirstRx() { return Download(first_, ns_); }
+  // per recv record: the send record it belongs to, or MGENX_MATCH_NONE
+  std::vector<uint32_t> RecvSend() { return Download(rs_, nr_); }
+  Flow* DevFlows() const { return flows_.data(); }
+
+ private:
+  void Upload(DeviceArray<uint32_t>& d, const std::vector<uint32_t>& h, uint32_t n,
+              hipStream_t st) {
+    if (h.size() != n) throw Error("MessageMatch: columns of unequal length");
+    d.Resize(n);
+    if (n) check_hip(hipMemcpyAsync(d.data(), h.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "H2D");
+  }
+  template <typename T>
+  std::vector<T> Download(const DeviceArray<T>& d, size_t n) {
+    std::vector<T> out(n);
+    if (n)
+      check_hip(hipMemcpyAsync(out.data(), d.data(), n * sizeof(T), hipMemcpyDeviceToHost,
+                               ctx_.stream()), "D2H");
+    ctx_.Sync();
+    return out;
+  }
+  Context& ctx_;
+  uint32_t n_flows_, opts_, ns_ = 0, nr_ = 0;
+  DeviceArray<Flow> flows_;
+  DeviceArray<Stats> stats_;
+  DeviceArray<uint32_t> d_s_[5], d_r_[6], cnt_, first_, rs_;
+};
+
 // ---- sharded stream framing: one TCP / SINK stream over the ranks of a job --------------
 // An all-gather of fixed-size u64 vectors among the ranks (host vectors in and out):
 // out[r * in.size() + k] = rank r's in[k].  The framing exchanges two kinds of message:

@@ -31,6 +31,7 @@ from ._abi import (  # noqa: F401
     FLOW_DIST_BINS, FLOW_DIST_DTYPE, FLOW_SERIES_BIN_DTYPE, FLOW_SERIES_STATE_DTYPE,
     ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
     PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
+    MATCH_NONE, MATCH_NO_TIME, MATCH_RUN_BINS, FLOW_MATCH_DTYPE, MATCH_STATS_DTYPE,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -61,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_flow_series_init", "mgenx_flow_series",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
+    "mgenx_match_side", "mgenx_msg_match",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -170,6 +172,9 @@ def load(diag: bool = False):
     L.mgenx_flow_series_init.argtypes = [P, P, P, u32, u32, P]
     L.mgenx_flow_series.argtypes = [P, P, P, P, P, P, P, P, u32, ctypes.c_int64, u64, u32, P, P,
                                     u32, P]
+    L.mgenx_match_side.argtypes = [P, P, P, P, u32, u32, P, P, P]
+    L.mgenx_msg_match.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P, P,
+                                  P, P, P]
     L.mgenx_flow_dist_bin.argtypes = [u64]
     L.mgenx_flow_dist_bin.restype = u32
     L.mgenx_flow_dist_bin_lo.argtypes = [u32]
@@ -679,6 +684,49 @@ class Engine:
                                                _ptr(rx_usec), n, int(t0_us), int(width_us),
                                                int(n_bins), _ptr(state), _ptr(bins), n_flows,
                                                _stream(self.device)), "mgenx_flow_series")
+
+    def match_side(self, parsed, n, want_event):
+        """A parsed log (log_parse_text) made ready for flow_lookup as one side of msg_match
+        (mgenx_match_side): returns (cols, src) where cols is `parsed` with err = 0 exactly for
+        the OK lines of want_event (EVENT_SEND / EVENT_RECV) and src holds the lines' source
+        ports with the addresses cleared, so a SEND line and the RECV line of its flow share
+        one key."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        err = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        src = torch.empty(max(n, 1) * ADDR_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._check(self.lib.mgenx_match_side(self.ctx, _ptr(parsed["event"]),
+                                              _ptr(parsed["status"]), _ptr(parsed["src"]), n,
+                                              want_event, _ptr(src), _ptr(err),
+                                              _stream(self.device)), "mgenx_match_side")
+        cols = dict(parsed)
+        cols["err"] = err
+        return cols, src
+
+    def msg_match(self, n_flows, send, recv, *, opts=0, ns=None, nr=None):
+        """Join a sender's records with a receiver's (mgenx_msg_match).  send: dict of int32
+        tensors flow_idx, seq, t_sec, t_usec, len; recv: flow_idx, seq, tx_sec, tx_usec, rx_sec,
+        rx_usec (flow indices from one numbering).  Returns (send_rx_count, send_first_rx,
+        recv_send, flows, stats): int32 tensors of ns, ns and nr elements and uint8 tensors of
+        n_flows x 256 B (FLOW_MATCH_DTYPE) and 32 B (MATCH_STATS_DTYPE)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        ns = send["flow_idx"].numel() if ns is None else ns
+        nr = recv["flow_idx"].numel() if nr is None else nr
+        cnt = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        rs = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
+        flows = torch.empty(max(n_flows, 1) * FLOW_MATCH_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        stats = torch.empty(MATCH_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._check(self.lib.mgenx_msg_match(
+            self.ctx, _ptr(send["flow_idx"]), _ptr(send["seq"]), _ptr(send["t_sec"]),
+            _ptr(send["t_usec"]), _ptr(send["len"]), ns, _ptr(recv["flow_idx"]),
+            _ptr(recv["seq"]), _ptr(recv["tx_sec"]), _ptr(recv["tx_usec"]), _ptr(recv["rx_sec"]),
+            _ptr(recv["rx_usec"]), nr, n_flows, opts, _ptr(cnt), _ptr(first), _ptr(rs),
+            _ptr(flows), _ptr(stats), _stream(self.device)), "mgenx_msg_match")
+        return (cnt[:ns], first[:ns], rs[:nr], flows[:n_flows * FLOW_MATCH_DTYPE.itemsize],
+                stats)
 
     def flow_keys(self, table, n_flows, protocol=1, keys=None):
         """The report_msg key of every flow index < n_flows (mgenx_flow_keys): a uint8
@@ -1294,6 +1342,88 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
                 state.cpu().numpy().view(FLOW_SERIES_STATE_DTYPE).copy(),
                 bins.cpu().numpy().view(FLOW_SERIES_BIN_DTYPE).reshape(nf, n_bins).copy(),
                 t0_us, n, n_bad)
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
+        eng.close()
+
+
+def match_text_logs(send_log_bytes, recv_log_bytes, no_time=False, day_base=0, device=0) -> tuple:
+    """A sender's text log (SEND lines) joined with a receiver's (RECV lines) on the GPU: line
+    index -> parse -> match_side -> FindFlow on one table, sender first -> mgenx_msg_match.
+    Returns (keys, flows, stats, send_rx_count, send_first_rx, recv_send, n_send_flows): numpy
+    arrays of REPORT_KEY_DTYPE and FLOW_MATCH_DTYPE [n_flows], one MATCH_STATS_DTYPE element,
+    and uint32 arrays with one element per line of the sender's log (the first two) and of the
+    receiver's.  Flows are numbered by their first SEND line; the receiver-only flows follow
+    from index n_send_flows.  The keys' source addresses are cleared (a SEND line has the port
+    only) and their protocol is that of the first OK SEND line."""
+    import torch
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+
+        def side(log, want):
+            raw = np.frombuffer(bytes(log), np.uint8)
+            n = 0
+            if raw.size:
+                text = torch.from_numpy(raw.copy()).to(dev)
+                line_off, n = eng.text_index(text)
+            if n == 0:
+                return None, None, 0
+            p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+            cols, src = eng.match_side(p, n, want)
+            return cols, src, n
+
+        s, s_src, ns = side(send_log_bytes, EVENT_SEND)
+        r, r_src, nr = side(recv_log_bytes, EVENT_RECV)
+        none = torch.zeros(0, dtype=torch.int32, device=dev)
+        s_idx = r_idx = none
+        nf = n_send = 0
+        cap = max(ns + nr, 16)
+        while ns + nr:
+            # FLOW_NONE on an OK line means "redo on a larger table", never "no such flow"
+            table = eng.flow_table(cap)
+            refused = False
+            if ns:
+                s_idx, n_flows = eng.flow_lookup(table, s, s_src, ns)
+                n_send = int(n_flows.item())
+                refused = bool(((s["err"][:ns] == 0) & (s_idx == -1)).any().item())
+            nf = n_send
+            if nr and not refused:
+                r_idx, n_flows = eng.flow_lookup(table, r, r_src, nr)
+                nf = int(n_flows.item())
+                refused = bool(((r["err"][:nr] == 0) & (r_idx == -1)).any().item())
+            if not refused:
+                break
+            eng.flow_table_destroy(table)
+            table = None
+            cap *= 4
+        send = dict(flow_idx=s_idx, seq=none, t_sec=none, t_usec=none, len=none)
+        if ns:
+            send.update(seq=s["seq_num"], t_sec=s["rx_sec"], t_usec=s["rx_usec"], len=s["size"])
+        recv = dict(flow_idx=r_idx, seq=none, tx_sec=none, tx_usec=none, rx_sec=none, rx_usec=none)
+        if nr:
+            recv.update(seq=r["seq_num"], tx_sec=r["tx_sec"], tx_usec=r["tx_usec"],
+                        rx_sec=r["rx_sec"], rx_usec=r["rx_usec"])
+        cnt, first, rs, flows, stats = eng.msg_match(
+            nf, send, recv, opts=MATCH_NO_TIME if no_time else 0, ns=ns, nr=nr)
+        keys = np.zeros(0, REPORT_KEY_DTYPE)
+        if nf:
+            proto = 1
+            for p in (s, r):
+                if p is not None:
+                    ok = p["protocol"][p["err"] == 0]
+                    if ok.numel():
+                        proto = int(ok[0].item())
+                        break
+            keys = eng.flow_keys(table, nf, protocol=proto).cpu().numpy().view(
+                REPORT_KEY_DTYPE)[:nf].copy()
+        torch.cuda.synchronize(device)
+        u32 = lambda t: t.cpu().numpy().view(np.uint32).copy()  # noqa: E731
+        return (keys, flows.cpu().numpy().view(FLOW_MATCH_DTYPE).copy(),
+                stats.cpu().numpy().view(MATCH_STATS_DTYPE)[0].copy(), u32(cnt), u32(first),
+                u32(rs), n_send)
     finally:
         if table is not None:
             eng.flow_table_destroy(table)

@@ -158,6 +158,21 @@ FLOW_SERIES_STATE_DTYPE = np.dtype([
     ("n", "<u8"), ("last_lat", "<i8"), ("outside", "<u8"), ("seq_max", "<u4"), ("rsv", "<u4")])
 assert FLOW_SERIES_BIN_DTYPE.itemsize == 64 and FLOW_SERIES_STATE_DTYPE.itemsize == 32
 
+# ---- sender log joined with receiver log (mgenx_msg_match, include/mgenx.h) ----
+MATCH_NONE = 0xFFFFFFFF   # MGENX_MATCH_NONE
+MATCH_NO_TIME = 0x1       # MGENX_MATCH_NO_TIME
+MATCH_RUN_BINS = 18
+FLOW_MATCH_DTYPE = np.dtype([
+    ("sent", "<u8"), ("sent_bytes", "<u8"), ("send_dup", "<u8"), ("delivered", "<u8"),
+    ("delivered_bytes", "<u8"), ("rx_dup", "<u8"), ("rx_orphan", "<u8"), ("lost_head", "<u8"),
+    ("lost_tail", "<u8"), ("loss_runs", "<u8"), ("loss_run_max", "<u8"),
+    ("loss_run_hist", "<u8", (MATCH_RUN_BINS,)), ("lat_sum", "<i8"), ("lat_min", "<i8"),
+    ("lat_max", "<i8")])
+MATCH_STATS_DTYPE = np.dtype([
+    ("send_skipped", "<u8"), ("recv_skipped", "<u8"), ("recv_unmatched", "<u8"),
+    ("send_dup", "<u8")])
+assert FLOW_MATCH_DTYPE.itemsize == 256 and MATCH_STATS_DTYPE.itemsize == 32
+
 
 # ---- pcap2mgen / text interleave (include/mgenx.h) ----
 class PcapInfo(ctypes.Structure):      # mgenx_pcap_info

@@ -169,6 +169,21 @@ extern "C" int mgenx_flow_series_run(void* ws, const uint32_t* flow_idx, const u
                                      struct mgenx_flow_series_state* state,
                                      struct mgenx_flow_series_bin* bins, uint32_t n_flows,
                                      hipStream_t stream, char* err, size_t errn);
+extern "C" void* mgenx_match_ws_new();
+extern "C" void mgenx_match_ws_free(void* p);
+extern "C" int mgenx_match_side_run(const uint8_t* event, const uint8_t* status,
+                                    const mgenx_addr* src, uint32_t n, uint32_t want_event,
+                                    mgenx_addr* src_out, uint8_t* err_out, hipStream_t stream);
+extern "C" int mgenx_msg_match_run(void* ws, const uint32_t* s_flow, const uint32_t* s_seq,
+                                   const uint32_t* s_sec, const uint32_t* s_usec,
+                                   const uint32_t* s_len, uint32_t ns, const uint32_t* r_flow,
+                                   const uint32_t* r_seq, const uint32_t* r_txs,
+                                   const uint32_t* r_txu, const uint32_t* r_rxs,
+                                   const uint32_t* r_rxu, uint32_t nr, uint32_t n_flows,
+                                   uint32_t opts, uint32_t* send_rx_count, uint32_t* send_first_rx,
+                                   uint32_t* recv_send, struct mgenx_flow_match* flows,
+                                   struct mgenx_match_stats* stats, hipStream_t stream, char* err,
+                                   size_t errn);
 extern "C" int mgenx_flow_dist_quantiles_run(const struct mgenx_flow_dist* dist,
                                              const uint64_t* hist, uint32_t n_flows,
                                              const uint32_t* permille, uint32_t n_q, int64_t* out,
@@ -235,6 +250,7 @@ struct mgenx_ctx {
   void* flow_ws = nullptr;        // flow-reduce workspace (mgenx_analytic.hip), grown on demand
   void* flowdist_ws = nullptr;    // flow-dist workspace (mgenx_flowdist.hip), grown on demand
   void* flowseries_ws = nullptr;  // flow-series workspace (mgenx_flowseries.hip), grown on demand
+  void* match_ws = nullptr;       // msg-match workspace (mgenx_match.hip), grown on demand
   void* log_ws = nullptr;         // log-format workspace (mgenx_log.hip), grown on demand
   void* tcp_ws = nullptr;         // TCP transmit workspace (mgenx_pack_tcp), grown on demand
   size_t tcp_ws_bytes = 0;
@@ -442,6 +458,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   if (c->flow_ws) mgenx_flow_ws_free(c->flow_ws);
   if (c->flowdist_ws) mgenx_flowdist_ws_free(c->flowdist_ws);
   if (c->flowseries_ws) mgenx_flowseries_ws_free(c->flowseries_ws);
+  if (c->match_ws) mgenx_match_ws_free(c->match_ws);
   if (c->log_ws) mgenx_log_ws_free(c->log_ws);
   mgenx::dev_free(c->tcp_ws);
   mgenx::dev_free(c->tcp_plan);
@@ -1030,6 +1047,46 @@ int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32
                                dev_msg_len, dev_rx_sec, dev_rx_usec, n, t0_us, width_us, n_bins,
                                dev_state, dev_bins, n_flows, (hipStream_t)stream, ctx->err,
                                sizeof(ctx->err));
+}
+
+int mgenx_match_side(mgenx_ctx* ctx, const uint8_t* dev_event, const uint8_t* dev_status,
+                     const mgenx_addr* dev_src, uint32_t n, uint32_t want_event,
+                     mgenx_addr* dev_src_out, uint8_t* dev_err_out, void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n == 0) return MGENX_OK;
+  if (!dev_event || !dev_status || !dev_src || !dev_src_out || !dev_err_out) return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return mgenx_match_side_run(dev_event, dev_status, dev_src, n, want_event, dev_src_out,
+                              dev_err_out, (hipStream_t)stream);
+}
+
+int mgenx_msg_match(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                    const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                    const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len, uint32_t ns,
+                    const uint32_t* dev_recv_flow_idx, const uint32_t* dev_recv_seq,
+                    const uint32_t* dev_recv_tx_sec, const uint32_t* dev_recv_tx_usec,
+                    const uint32_t* dev_recv_rx_sec, const uint32_t* dev_recv_rx_usec,
+                    uint32_t nr, uint32_t n_flows, uint32_t opts, uint32_t* dev_send_rx_count,
+                    uint32_t* dev_send_first_rx, uint32_t* dev_recv_send,
+                    struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
+                    void* stream) {
+  if (!ctx || !dev_stats || ns > (1u << 30) || nr > 0x7FFFFFFFu || n_flows > 0x7FFFFFFFu)
+    return MGENX_EINVAL;
+  if (ns && (!dev_send_flow_idx || !dev_send_seq || !dev_send_t_sec || !dev_send_t_usec ||
+             !dev_send_len || !dev_send_rx_count || !dev_send_first_rx))
+    return MGENX_EINVAL;
+  if (nr && (!dev_recv_flow_idx || !dev_recv_seq || !dev_recv_tx_sec || !dev_recv_tx_usec ||
+             !dev_recv_rx_sec || !dev_recv_rx_usec || !dev_recv_send))
+    return MGENX_EINVAL;
+  if (n_flows && !dev_flows) return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (!ctx->match_ws) ctx->match_ws = mgenx_match_ws_new();
+  return mgenx_msg_match_run(ctx->match_ws, dev_send_flow_idx, dev_send_seq, dev_send_t_sec,
+                             dev_send_t_usec, dev_send_len, ns, dev_recv_flow_idx, dev_recv_seq,
+                             dev_recv_tx_sec, dev_recv_tx_usec, dev_recv_rx_sec, dev_recv_rx_usec,
+                             nr, n_flows, opts, dev_send_rx_count, dev_send_first_rx,
+                             dev_recv_send, dev_flows, dev_stats, (hipStream_t)stream, ctx->err,
+                             sizeof(ctx->err));
 }
 
 static int log_recv(mgenx_ctx* ctx, bool binary, const uint8_t* dev_slab, uint64_t slab_bytes,

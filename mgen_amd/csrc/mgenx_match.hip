@@ -1,0 +1,658 @@
+// mgenx_match.hip -- a sender's log joined with a receiver's log on gfx950 (mgenx_msg_match,
+// mgenx_match_side; include/mgenx.h): an equi-join of two record sets on the message identity,
+// then per-flow delivery accounting in the sender's order.
+//
+//   0. match_init_kernel writes the empty per-flow values, zeroes the global counters and
+//      empties the hash table;
+//   1. match_build_kernel: a lane per send record.  An open-addressing table of send indices
+//      (a power of two >= 2 ns slots of 4 B, kEmpty = no record), linear probing from a 64-bit
+//      mix of the identity.  A lane takes an empty slot with a compare-and-swap; on a slot whose
+//      record has the equal identity (compared through the columns, never through the hash) it
+//      atomicMin's its own index in.  Equal identities share one probe sequence and a slot never
+//      changes identity, so each identity ends in exactly one slot holding its lowest index,
+//      whatever the interleaving.  Only atomics touch the table inside this launch; the probe
+//      loop is bounded by the slot count and no lane waits on another;
+//   2. match_mark_kernel: own[i] = the index its identity's slot holds (i itself for an owner);
+//   3. match_probe_kernel: a lane per recv record finds the owner or none, writes recv_send,
+//      counts into send_rx_count (atomicAdd) and send_first_rx (atomicMin); the orphans of a
+//      flow and the global counters are summed per wave before their atomics;
+//   4. the send records ordered by flow, stably (mgenx_flow_sort_run, as mgenx_flow_dist runs
+//      it), and cut into chunks of kChunk sorted positions that ignore the flow edges.
+//      Every position is U (an undelivered owner), D (a delivered owner) or X (a send
+//      duplicate, which neither counts nor breaks a run).  A loss run is a segment of a
+//      segmented sum of the U flags, segments starting at a flow's first position and at every
+//      D; bit 31 of the summed word marks a segment that started with its flow (no D yet).
+//      match_pack_kernel classifies, leaves one 16-B record per position and per chunk the sum
+//      after its last segment start and whether it has one; match_carry_kernel (one workgroup)
+//      scans those over the chunks; match_main_kernel repeats the scan with the carry and
+//      counts a run once, where it ends: at the D that follows it, or at the flow's last
+//      position.  lost_head and lost_tail fall out of the same word and have one writer per
+//      flow.  The other fields are reduced per run of a flow inside the chunk (a second
+//      segmented scan; the 18 histogram counts ride along as 12-bit fields of four words) and
+//      go out as one atomic per field that is not its identity.  Integer sums, minima and
+//      maxima commute, so the bytes left do not depend on the order the workgroups finish in.
+#include <hip/hip_runtime.h>
+
+#include <limits.h>
+#include <stdio.h>
+
+#include "mgenx_flowdist.hpp"
+#include "mgenx_kernels.hpp"
+
+namespace mgenx {
+
+typedef struct mgenx_flow_match FlowMatch;
+typedef struct mgenx_match_stats MatchStats;
+static_assert(sizeof(FlowMatch) == 256, "mgenx_flow_match is 256 B");
+static_assert(sizeof(MatchStats) == 32, "mgenx_match_stats is 32 B");
+
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;      // an empty slot; MGENX_MATCH_NONE in the outputs
+constexpr uint32_t kFromFlowStart = 1u << 31;  // the segment began with its flow: no D yet
+constexpr uint32_t kLenMask = kFromFlowStart - 1u;
+enum : uint8_t { kX = 0, kU = 1, kD = 2 };
+
+struct MatchSide {  // the identity columns of one side
+  const uint32_t *flow, *seq, *sec, *usec;
+};
+
+// one sorted position as the main pass reads it
+struct alignas(16) MatchRec {
+  int64_t lat;   // D only
+  uint32_t len;  // U and D
+  uint32_t rxc;  // D: send_rx_count
+};
+static_assert(sizeof(MatchRec) == 16, "MatchRec is 16 B");
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+struct Ident {
+  uint32_t flow, seq, sec, usec;
+};
+__device__ __forceinline__ Ident ident_of(const MatchSide& s, uint32_t i, bool use_time) {
+  Ident d;
+  d.flow = s.flow[i];
+  d.seq = s.seq[i];
+  d.sec = use_time ? s.sec[i] : 0u;
+  d.usec = use_time ? s.usec[i] : 0u;
+  return d;
+}
+__device__ __forceinline__ bool ident_eq(const Ident& a, const Ident& b) {
+  return a.flow == b.flow && a.seq == b.seq && a.sec == b.sec && a.usec == b.usec;
+}
+__device__ __forceinline__ uint32_t ident_slot(const Ident& d, uint32_t mask) {
+  const uint64_t a = ((uint64_t)d.flow << 32) | d.seq, b = ((uint64_t)d.sec << 32) | d.usec;
+  return (uint32_t)mix64(mix64(a) ^ (b * 0x9E3779B97F4A7C15ull)) & mask;
+}
+
+// the slot's record index for identity `d`, or kEmpty (the table is complete: plain loads)
+__device__ __forceinline__ uint32_t table_find(const uint32_t* __restrict__ table, uint32_t mask,
+                                               const MatchSide& send, bool use_time,
+                                               const Ident& d) {
+  uint32_t slot = ident_slot(d, mask);
+  for (uint32_t k = 0; k <= mask; k++) {
+    const uint32_t v = table[slot];
+    if (v == kEmpty) return kEmpty;
+    if (ident_eq(ident_of(send, v, use_time), d)) return v;
+    slot = (slot + 1u) & mask;
+  }
+  return kEmpty;
+}
+
+// the sum of the lanes' counts of one wave, added by its first lane
+__device__ __forceinline__ void wave_count_add(uint64_t* dst, bool flag) {
+  const unsigned long long m = __ballot(flag);
+  if (m && (threadIdx.x & 63u) == 0u)
+    atomicAdd((unsigned long long*)dst, (unsigned long long)__popcll(m));
+}
+
+__global__ void match_init_kernel(FlowMatch* flows, uint32_t n_flows, MatchStats* stats,
+                                  uint32_t* table, uint32_t n_slots) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_flows) {
+    FlowMatch f = {};
+    f.lat_min = INT64_MAX;
+    f.lat_max = INT64_MIN;
+    flows[i] = f;
+  }
+  if (i < n_slots) table[i] = kEmpty;
+  if (i == 0) {
+    MatchStats s = {};
+    *stats = s;
+  }
+}
+
+__global__ void match_build_kernel(MatchSide send, uint32_t ns, uint32_t n_flows, bool use_time,
+                                   uint32_t* table, uint32_t mask, uint32_t* send_rx_count,
+                                   uint32_t* send_first_rx) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  send_rx_count[i] = 0u;
+  send_first_rx[i] = kEmpty;
+  if (send.flow[i] >= n_flows) return;
+  const Ident me = ident_of(send, i, use_time);
+  uint32_t slot = ident_slot(me, mask);
+  // (at most ns identities in more than ns slots: an empty slot or the identity's own comes up)
+  for (uint32_t k = 0; k <= mask; k++) {
+    const uint32_t v = atomicCAS(&table[slot], kEmpty, i);
+    if (v == kEmpty) return;
+    if (ident_eq(ident_of(send, v, use_time), me)) {
+      if (i < v) atomicMin(&table[slot], i);
+      return;
+    }
+    slot = (slot + 1u) & mask;
+  }
+}
+
+__global__ void match_mark_kernel(MatchSide send, uint32_t ns, uint32_t n_flows, bool use_time,
+                                  const uint32_t* __restrict__ table, uint32_t mask,
+                                  uint32_t* __restrict__ own, MatchStats* stats) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool skipped = false, dup = false;
+  if (i < ns) {
+    uint32_t o = kEmpty;
+    if (send.flow[i] >= n_flows) {
+      skipped = true;
+    } else {
+      o = table_find(table, mask, send, use_time, ident_of(send, i, use_time));
+      dup = o != i;
+    }
+    own[i] = o;
+  }
+  wave_count_add(&stats->send_skipped, skipped);
+  wave_count_add(&stats->send_dup, dup);
+}
+
+__global__ void match_probe_kernel(MatchSide send, MatchSide recv, uint32_t nr, uint32_t n_flows,
+                                   bool use_time, const uint32_t* __restrict__ table,
+                                   uint32_t mask, uint32_t* send_rx_count, uint32_t* send_first_rx,
+                                   uint32_t* __restrict__ recv_send, FlowMatch* flows,
+                                   MatchStats* stats) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  bool skipped = false, orphan = false;
+  uint32_t f = 0;
+  if (j < nr) {
+    f = recv.flow[j];
+    uint32_t o = kEmpty;
+    if (f >= n_flows) {
+      skipped = true;
+    } else {
+      o = table_find(table, mask, send, use_time, ident_of(recv, j, use_time));
+      if (o == kEmpty) {
+        orphan = true;
+      } else {
+        atomicAdd(&send_rx_count[o], 1u);
+        atomicMin(&send_first_rx[o], j);
+      }
+    }
+    recv_send[j] = o;
+  }
+  wave_count_add(&stats->recv_skipped, skipped);
+  wave_count_add(&stats->recv_unmatched, orphan);
+  // the orphans of one flow among the wave's lanes: one add per flow
+  unsigned long long left = __ballot(orphan);
+  const uint32_t lane = threadIdx.x & 63u;
+  while (left) {
+    const uint32_t lead = (uint32_t)__builtin_ctzll(left);
+    const uint32_t lf = __shfl(f, lead);
+    const unsigned long long same = __ballot(orphan && f == lf) & left;
+    if (lane == lead)
+      atomicAdd((unsigned long long*)&flows[lf].rx_orphan, (unsigned long long)__popcll(same));
+    left &= ~same;
+  }
+}
+
+// ---- segmented inclusive sum over the kChunk lanes of a workgroup ----
+// `head` starts a segment at this lane.  Returns the sum of v over the lanes from the lane's
+// segment start (or lane 0) to the lane; *open = no segment starts at or before it.
+// s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
+__device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t* s_v,
+                                                 uint32_t* s_h, bool* open) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint32_t h = head ? 1u : 0u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t pv = __shfl_up(v, d);
+    const uint32_t ph = __shfl_up(h, d);
+    if (lane >= d && !h) {
+      v += pv;
+      h = ph;
+    }
+  }
+  if (lane == 63u) {
+    s_v[w] = v;
+    s_h[w] = h;
+  }
+  __syncthreads();
+  if (w == 0) {
+    uint32_t wv = lane < kWaves ? s_v[lane] : 0u;
+    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
+#pragma unroll
+    for (uint32_t d = 1; d < kWaves; d <<= 1) {
+      const uint32_t pv = __shfl_up(wv, d);
+      const uint32_t ph = __shfl_up(wh, d);
+      if (lane >= d && !wh) {
+        wv += pv;
+        wh = ph;
+      }
+    }
+    if (lane < kWaves) {
+      s_v[lane] = wv;
+      s_h[lane] = wh;
+    }
+  }
+  __syncthreads();
+  if (w > 0 && !h) {
+    v += s_v[w - 1];
+    h = s_h[w - 1];
+  }
+  *open = h == 0u;
+  __syncthreads();
+  return v;
+}
+
+// a position's word in the loss-run scan and whether it starts a segment
+__device__ __forceinline__ uint32_t run_word(uint8_t cls, bool head_flow, bool* head) {
+  *head = head_flow || cls == kD;
+  if (cls == kD) return 0u;
+  return (cls == kU ? 1u : 0u) | (head_flow ? kFromFlowStart : 0u);
+}
+
+struct PackCols {
+  const uint32_t *own, *rx_count, *first_rx, *len, *t_sec, *t_usec, *rx_sec, *rx_usec;
+};
+
+// pass 4a: classify, pack, and the chunk's summary
+__global__ void __launch_bounds__(kChunk)
+match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
+                  const uint32_t* __restrict__ bnd, uint32_t n_flows, PackCols col,
+                  MatchRec* __restrict__ rec, uint8_t* __restrict__ cls_out,
+                  uint32_t* __restrict__ trail, uint32_t* __restrict__ has_head) {
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  const uint32_t c = blockIdx.x, t = threadIdx.x;
+  const uint32_t nv = bnd[n_flows];
+  const uint64_t p0 = (uint64_t)c * kChunk;
+  if (p0 >= nv) {  // no counted record here
+    if (t == 0) {
+      trail[c] = 0u;
+      has_head[c] = 1u;
+    }
+    return;
+  }
+  const uint32_t p = (uint32_t)p0 + t;
+  const bool active = p < nv;
+  uint8_t cls = kX;
+  bool head = true;
+  uint32_t v = 0u;
+  if (active) {
+    const uint32_t f = keys[p], i = order[p];
+    MatchRec r = {0, 0u, 0u};
+    if (col.own[i] == i) {
+      const uint32_t cnt = col.rx_count[i];
+      r.len = col.len[i];
+      if (cnt) {
+        const uint32_t j = col.first_rx[i];
+        cls = kD;
+        r.rxc = cnt;
+        r.lat = ((int64_t)col.rx_sec[j] - (int64_t)col.t_sec[i]) * 1000000 +
+                (int64_t)col.rx_usec[j] - (int64_t)col.t_usec[i];
+      } else {
+        cls = kU;
+      }
+    }
+    rec[p] = r;
+    cls_out[p] = cls;
+    v = run_word(cls, p == bnd[f], &head);
+  }
+  bool open;
+  const uint32_t incl = block_segsum(v, head, s_v, s_h, &open);
+  const int any = __syncthreads_or(active && head);
+  const uint32_t last = (uint32_t)min((uint64_t)nv - p0, (uint64_t)kChunk) - 1u;
+  if (t == last) {
+    trail[c] = incl;
+    has_head[c] = any ? 1u : 0u;
+  }
+}
+
+// pass 4b (one workgroup): carry[c] = the run word after chunk c's last position, over chunk c
+// and the chunks before it back to the last segment start
+__global__ void __launch_bounds__(kChunk)
+match_carry_kernel(const uint32_t* __restrict__ trail, const uint32_t* __restrict__ has_head,
+                   uint32_t n_chunks, uint32_t* __restrict__ carry) {
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  __shared__ uint32_t s_run;
+  const uint32_t t = threadIdx.x;
+  if (t == 0) s_run = 0u;
+  __syncthreads();
+  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
+    const uint32_t c = base + t;
+    const bool in = c < n_chunks;
+    uint32_t v = in ? trail[c] : 0u;
+    const bool head = in ? has_head[c] != 0u : true;
+    bool open;
+    v = block_segsum(v, head, s_v, s_h, &open);
+    if (open) v += s_run;
+    if (in) carry[c] = v;
+    __syncthreads();  // every lane has read s_run
+    if (t == kChunk - 1u) s_run = v;
+    __syncthreads();
+  }
+}
+
+// the terms of one position, or of a run of positions of one flow
+struct MatchAcc {
+  uint64_t cnt;  // sent | send_dup << 16 | delivered << 32 | loss_runs << 48: at most kChunk each
+  uint64_t sent_bytes, delivered_bytes, rx_dup, lat_sum, run_max;
+  int64_t lat_min, lat_max;
+  uint64_t hist[4];  // loss_run_hist[k] in bits 12 (k % 5) .. of word k / 5: at most kChunk each
+};
+
+__device__ __forceinline__ void acc_add(MatchAcc& a, const MatchAcc& b) {
+  a.cnt += b.cnt;
+  a.sent_bytes += b.sent_bytes;
+  a.delivered_bytes += b.delivered_bytes;
+  a.rx_dup += b.rx_dup;
+  a.lat_sum += b.lat_sum;
+  a.run_max = a.run_max > b.run_max ? a.run_max : b.run_max;
+  a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
+  a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
+#pragma unroll
+  for (int k = 0; k < 4; k++) a.hist[k] += b.hist[k];
+}
+
+__device__ __forceinline__ MatchAcc acc_shfl_up(const MatchAcc& a, uint32_t d) {
+  typedef unsigned long long ull;
+  MatchAcc o;
+  o.cnt = __shfl_up((ull)a.cnt, d);
+  o.sent_bytes = __shfl_up((ull)a.sent_bytes, d);
+  o.delivered_bytes = __shfl_up((ull)a.delivered_bytes, d);
+  o.rx_dup = __shfl_up((ull)a.rx_dup, d);
+  o.lat_sum = __shfl_up((ull)a.lat_sum, d);
+  o.run_max = __shfl_up((ull)a.run_max, d);
+  o.lat_min = __shfl_up((long long)a.lat_min, d);
+  o.lat_max = __shfl_up((long long)a.lat_max, d);
+#pragma unroll
+  for (int k = 0; k < 4; k++) o.hist[k] = __shfl_up((ull)a.hist[k], d);
+  return o;
+}
+
+// segmented inclusive scan of the terms over the kChunk lanes (mgenx_flowseries.hip's shape)
+__device__ __forceinline__ void block_segscan(MatchAcc& a, bool head, MatchAcc* s_a,
+                                              uint32_t* s_h) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint32_t h = head ? 1u : 0u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const MatchAcc pa = acc_shfl_up(a, d);
+    const uint32_t ph = __shfl_up(h, d);
+    if (lane >= d && !h) {
+      acc_add(a, pa);
+      h = ph;
+    }
+  }
+  if (lane == 63u) {
+    s_a[w] = a;
+    s_h[w] = h;
+  }
+  __syncthreads();
+  if (w == 0) {
+    MatchAcc wa = s_a[lane < kWaves ? lane : 0u];
+    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
+#pragma unroll
+    for (uint32_t d = 1; d < kWaves; d <<= 1) {
+      const MatchAcc pa = acc_shfl_up(wa, d);
+      const uint32_t ph = __shfl_up(wh, d);
+      if (lane >= d && !wh) {
+        acc_add(wa, pa);
+        wh = ph;
+      }
+    }
+    if (lane < kWaves) s_a[lane] = wa;
+  }
+  __syncthreads();
+  if (w > 0 && !h) acc_add(a, s_a[w - 1]);  // the run started in an earlier wave
+}
+
+// pass 4c: the accounting.  A lane per sorted position.
+__global__ void __launch_bounds__(kChunk)
+match_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ bnd,
+                  uint32_t n_flows, const MatchRec* __restrict__ rec,
+                  const uint8_t* __restrict__ cls_in, const uint32_t* __restrict__ carry,
+                  FlowMatch* flows) {
+  typedef unsigned long long ull;
+  __shared__ uint32_t s_incl[kChunk], s_key[kChunk];
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  __shared__ MatchAcc s_a[kWaves];
+
+  const uint32_t c = blockIdx.x, t = threadIdx.x;
+  const uint32_t nv = bnd[n_flows];
+  const uint64_t p0 = (uint64_t)c * kChunk;
+  if (p0 >= nv) return;  // (the whole workgroup)
+  const uint32_t p = (uint32_t)p0 + t;
+  const bool active = p < nv;
+
+  uint32_t f = kEmpty;
+  uint8_t cls = kX;
+  bool head_flow = false, tail_flow = false, head = true;
+  MatchRec me = {0, 0u, 0u};
+  uint32_t v = 0u, cin = 0u;
+  if (active) {
+    f = keys[p];
+    head_flow = p == bnd[f];
+    tail_flow = p == bnd[f + 1u] - 1u;
+    cls = cls_in[p];
+    me = rec[p];
+    v = run_word(cls, head_flow, &head);
+    // the chunk's first position inside a flow continues the chunks before it (c > 0)
+    if (t == 0u && !head_flow) {
+      cin = carry[c - 1u];
+      if (cls != kD) v += cin;
+    }
+  }
+  s_key[t] = f;
+  bool open;
+  const uint32_t incl = block_segsum(v, head, s_v, s_h, &open);
+  s_incl[t] = incl;
+  __syncthreads();
+
+  MatchAcc a = {0, 0, 0, 0, 0, 0, INT64_MAX, INT64_MIN, {0, 0, 0, 0}};
+  bool run_head = true, run_tail = false;
+  if (active) {
+    // a loss run is counted where it ends: at the D after it, or at the flow's last position
+    uint32_t ended = 0u;
+    if (cls == kD)
+      ended = head_flow ? 0u : t == 0u ? cin : s_incl[t - 1u];
+    else if (tail_flow)
+      ended = incl;
+    const uint32_t run = ended & kLenMask;
+    FlowMatch* d = flows + f;
+    if (run) {
+      // one writer per flow and field: the first D of the flow, or its last position
+      if (ended & kFromFlowStart)
+        d->lost_head = run;
+      else if (cls != kD)
+        d->lost_tail = run;
+      const uint32_t k = min(31u - (uint32_t)__builtin_clz(run), 17u);
+      // (static indices: a runtime one would put the terms in scratch memory)
+#pragma unroll
+      for (uint32_t w = 0; w < 4u; w++) a.hist[w] = k / 5u == w ? 1ull << (12u * (k % 5u)) : 0ull;
+      a.run_max = run;
+    }
+    a.cnt = (uint64_t)(cls != kX) | ((uint64_t)(cls == kX) << 16) | ((uint64_t)(cls == kD) << 32) |
+            ((uint64_t)(run != 0u) << 48);
+    a.sent_bytes = me.len;
+    if (cls == kD) {
+      a.delivered_bytes = me.len;
+      a.rx_dup = me.rxc - 1u;
+      a.lat_sum = (uint64_t)me.lat;
+      a.lat_min = a.lat_max = me.lat;
+    }
+    run_head = t == 0u || s_key[t - 1u] != f;
+    run_tail = t == kChunk - 1u || s_key[t + 1u] != f;
+  }
+  block_segscan(a, run_head, s_a, s_h);
+
+  if (active && run_tail) {
+    FlowMatch* d = flows + f;
+    const uint64_t sent = a.cnt & 0xFFFFu, dup = (a.cnt >> 16) & 0xFFFFu,
+                   dlv = (a.cnt >> 32) & 0xFFFFu, runs = a.cnt >> 48;
+    if (sent) atomicAdd((ull*)&d->sent, (ull)sent);
+    if (a.sent_bytes) atomicAdd((ull*)&d->sent_bytes, (ull)a.sent_bytes);
+    if (dup) atomicAdd((ull*)&d->send_dup, (ull)dup);
+    if (dlv) {
+      atomicAdd((ull*)&d->delivered, (ull)dlv);
+      if (a.delivered_bytes) atomicAdd((ull*)&d->delivered_bytes, (ull)a.delivered_bytes);
+      if (a.rx_dup) atomicAdd((ull*)&d->rx_dup, (ull)a.rx_dup);
+      if (a.lat_sum) atomicAdd((ull*)&d->lat_sum, (ull)a.lat_sum);
+      atomicMin((long long*)&d->lat_min, (long long)a.lat_min);
+      atomicMax((long long*)&d->lat_max, (long long)a.lat_max);
+    }
+    if (runs) {
+      atomicAdd((ull*)&d->loss_runs, (ull)runs);
+      atomicMax((ull*)&d->loss_run_max, (ull)a.run_max);
+#pragma unroll
+      for (uint32_t k = 0; k < 18u; k++) {
+        const uint64_t n = (a.hist[k / 5u] >> (12u * (k % 5u))) & 0xFFFu;
+        if (n) atomicAdd((ull*)&d->loss_run_hist[k], (ull)n);
+      }
+    }
+  }
+}
+
+// one lane per parsed line (mgenx_match_side; src_out may be src)
+__global__ void match_side_kernel(const uint8_t* __restrict__ event,
+                                  const uint8_t* __restrict__ status, const mgenx_addr* src,
+                                  uint32_t n, uint32_t want_event, mgenx_addr* src_out,
+                                  uint8_t* __restrict__ err_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  err_out[i] = (status[i] == MGENX_PARSE_OK && event[i] == want_event) ? 0
+                                                                      : MGENX_ERROR_NOT_RECV;
+  mgenx_addr a = {};
+  a.port = src[i].port;
+  src_out[i] = a;
+}
+
+}  // namespace mgenx
+
+// ------------------------------------------------------------------------------------
+// host side (workspace owned by the context; see mgenx_api.hip)
+// ------------------------------------------------------------------------------------
+using namespace mgenx;
+
+extern "C" size_t mgenx_flow_sort_ws(uint32_t n, uint32_t n_flows);
+extern "C" int mgenx_flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n,
+                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
+                                   const uint32_t** bnd, hipStream_t stream, char* err,
+                                   size_t errn);
+
+struct mgenx_match_ws {
+  void* mem = nullptr;
+  size_t bytes = 0;
+};
+
+extern "C" void* mgenx_match_ws_new() { return new mgenx_match_ws(); }
+extern "C" void mgenx_match_ws_free(void* p) {
+  mgenx_match_ws* w = static_cast<mgenx_match_ws*>(p);
+  if (!w) return;
+  mgenx::dev_free(w->mem);
+  delete w;
+}
+
+extern "C" int mgenx_match_side_run(const uint8_t* event, const uint8_t* status,
+                                    const mgenx_addr* src, uint32_t n, uint32_t want_event,
+                                    mgenx_addr* src_out, uint8_t* err_out, hipStream_t stream) {
+  hipLaunchKernelGGL(match_side_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, event,
+                     status, src, n, want_event, src_out, err_out);
+  return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
+}
+
+static size_t mm_a256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// ns <= 2^30 (the slot count fits 32 bits); nr, n_flows < 2^31
+extern "C" int mgenx_msg_match_run(void* wsp, const uint32_t* s_flow, const uint32_t* s_seq,
+                                   const uint32_t* s_sec, const uint32_t* s_usec,
+                                   const uint32_t* s_len, uint32_t ns, const uint32_t* r_flow,
+                                   const uint32_t* r_seq, const uint32_t* r_txs,
+                                   const uint32_t* r_txu, const uint32_t* r_rxs,
+                                   const uint32_t* r_rxu, uint32_t nr, uint32_t n_flows,
+                                   uint32_t opts, uint32_t* send_rx_count, uint32_t* send_first_rx,
+                                   uint32_t* recv_send, FlowMatch* flows, MatchStats* stats,
+                                   hipStream_t stream, char* err, size_t errn) {
+  mgenx_match_ws& ws = *static_cast<mgenx_match_ws*>(wsp);
+  uint32_t n_slots = 64;  // a power of two >= 2 ns
+  while (n_slots < 2u * ns) n_slots <<= 1;
+  const bool account = ns > 0 && n_flows > 0;
+  const uint32_t n_chunks = (ns + kChunk - 1u) / kChunk;
+  const size_t tab_b = mm_a256((size_t)n_slots * 4u), own_b = mm_a256((size_t)ns * 4u),
+               sort_b = account ? mm_a256(mgenx_flow_sort_ws(ns, n_flows)) : 0,
+               rec_b = mm_a256((size_t)ns * sizeof(MatchRec)), cls_b = mm_a256((size_t)ns),
+               c4 = mm_a256((size_t)n_chunks * 4u);
+  const size_t need = tab_b + own_b + sort_b + rec_b + cls_b + 3 * c4;
+  if (ws.bytes < need) {
+    mgenx::dev_free(ws.mem);
+    ws.mem = nullptr;
+    ws.bytes = 0;
+    if (hipMalloc(&ws.mem, need) != hipSuccess) {
+      snprintf(err, errn, "msg_match: workspace of %zu bytes", need);
+      return MGENX_EDEVICE;
+    }
+    ws.bytes = need;
+  }
+  char* p = static_cast<char*>(ws.mem);
+  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  uint32_t* table = (uint32_t*)take(tab_b);
+  uint32_t* own = (uint32_t*)take(own_b);
+  void* sort_mem = take(sort_b);
+  MatchRec* rec = (MatchRec*)take(rec_b);
+  uint8_t* cls = (uint8_t*)take(cls_b);
+  uint32_t* trail = (uint32_t*)take(c4);
+  uint32_t* has_head = (uint32_t*)take(c4);
+  uint32_t* carry = (uint32_t*)take(c4);
+
+  const bool use_time = !(opts & MGENX_MATCH_NO_TIME);
+  const uint32_t mask = n_slots - 1u;
+  const MatchSide send = {s_flow, s_seq, s_sec, s_usec}, recv = {r_flow, r_seq, r_txs, r_txu};
+  const uint32_t n_init = n_slots > n_flows ? n_slots : n_flows;
+  hipLaunchKernelGGL(match_init_kernel, dim3((n_init + 255u) / 256u), dim3(256), 0, stream, flows,
+                     n_flows, stats, table, n_slots);
+  if (ns) {
+    hipLaunchKernelGGL(match_build_kernel, dim3((ns + 255u) / 256u), dim3(256), 0, stream, send, ns,
+                       n_flows, use_time, table, mask, send_rx_count, send_first_rx);
+    hipLaunchKernelGGL(match_mark_kernel, dim3((ns + 255u) / 256u), dim3(256), 0, stream, send, ns,
+                       n_flows, use_time, table, mask, own, stats);
+  }
+  if (nr)
+    hipLaunchKernelGGL(match_probe_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, stream, send,
+                       recv, nr, n_flows, use_time, table, mask, send_rx_count, send_first_rx,
+                       recv_send, flows, stats);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(err, errn, "msg_match: %s", hipGetErrorString(e));
+    return MGENX_EDEVICE;
+  }
+  if (!account) return MGENX_OK;
+  const uint32_t *keys, *order, *bnd;
+  const int rc = mgenx_flow_sort_run(sort_mem, s_flow, ns, n_flows, &keys, &order, &bnd, stream,
+                                     err, errn);
+  if (rc != MGENX_OK) return rc;
+  const PackCols col = {own, send_rx_count, send_first_rx, s_len, s_sec, s_usec, r_rxs, r_rxu};
+  hipLaunchKernelGGL(match_pack_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, order, bnd,
+                     n_flows, col, rec, cls, trail, has_head);
+  hipLaunchKernelGGL(match_carry_kernel, dim3(1), dim3(kChunk), 0, stream, trail, has_head,
+                     n_chunks, carry);
+  hipLaunchKernelGGL(match_main_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, bnd,
+                     n_flows, rec, cls, carry, flows);
+  e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(err, errn, "msg_match: %s", hipGetErrorString(e));
+    return MGENX_EDEVICE;
+  }
+  return MGENX_OK;
+}
