@@ -17,6 +17,7 @@
 #include <chrono>
 #include <emmintrin.h>
 #include <atomic>
+#include <limits>
 #include <mutex>
 #include <vector>
 
@@ -330,11 +331,14 @@ void build_report_tables(double* rq) {
   for (int k = 0; k < 256; k++) rq[mgenx::kRqThrTime + k] = HUGE_VAL;
   for (int k = 2; k < 256; k++)
     rq[mgenx::kRqThrTime + k] = first_true(MN, S * MX, [&](double v) { return host_q_time(v) >= k; });
-  // rate exponent: (int)log10(r) >= e, e = kRqLog10Lo .. kRqLog10Lo + kRqLog10N - 1
+  // rate exponent: (int)log10(r) >= e, e = kRqLog10Lo .. kRqLog10Lo + kRqLog10N - 1, over
+  // every positive double (e = -324 and -323 both start at the smallest subnormal)
+  const double lo = std::numeric_limits<double>::denorm_min();
+  const double hi = std::numeric_limits<double>::max();
   for (int j = 0; j < mgenx::kRqLog10N; j++) {
     const int e = mgenx::kRqLog10Lo + j;
     rq[mgenx::kRqThrLog10 + j] =
-        first_true(1e-300, 1e300, [&](double v) { return (int32_t)log10(v) >= e; });
+        first_true(lo, hi, [&](double v) { return (int32_t)log10(v) >= e; });
   }
   for (int e = 0; e < mgenx::kRqP10N; e++) rq[mgenx::kRqP10 + e] = pow(10.0, (double)e);
 }

@@ -114,12 +114,12 @@ hipError_t launch_pack_prepare(const mgenx_flow_tmpl* tmpl, uint32_t n_tmpl, con
 // MgenAnalytic::Report quantizer tables (built on the host at context creation)
 constexpr int kRqUnqTime = 0;          // [256] UnquantizeTimeValue(q)
 constexpr int kRqThrTime = 256;        // [256] first value with QuantizeTimeValue >= k (k >= 2)
-constexpr int kRqLog10Lo = -40;        // (int)log10 thresholds for e = -40 .. 24
-constexpr int kRqLog10N = 65;
+constexpr int kRqLog10Lo = -324;       // (int)log10 thresholds for e = -324 .. 308: every
+constexpr int kRqLog10N = 633;         // positive double (the device's own log10 rounds apart)
 constexpr int kRqThrLog10 = 512;
-constexpr int kRqP10 = 512 + 65;       // [309] pow(10, e)
+constexpr int kRqP10 = kRqThrLog10 + kRqLog10N;  // [309] pow(10, e)
 constexpr int kRqP10N = 309;
-constexpr int kRqDoubles = 512 + 65 + 309;
+constexpr int kRqDoubles = kRqP10 + kRqP10N;
 
 // TCP receiver's persistent rx_msg (mgenx_rx.hip)
 hipError_t launch_rx_persist(const mgenx_cols& c, uint32_t n, uint32_t opts, int32_t* ws,

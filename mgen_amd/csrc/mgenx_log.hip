@@ -554,20 +554,16 @@ __device__ __forceinline__ double rq_uq_time(const Rq& r, uint8_t q) { return r.
 
 __device__ uint16_t rq_q_rate(const Rq& r, double rate) {
   if (rate <= 0.0) return 0x01;
-  // (UINT16)(int)log10(rate) from the host's thresholds; outside them the device's log10
+  // (UINT16)(int)log10(rate) from the host's thresholds, which span every positive double
+  // (T[0] is the smallest one): the device's own log10 rounds some doubles next to a power
+  // of ten to the other side.  Undefined in the reference: inf gives e = 308, nan e = -323.
   const double* T = r.t + kRqThrLog10;
-  int32_t e;
-  if (rate < T[0] || !(rate < T[kRqLog10N - 1])) {
-    e = (int32_t)log10(rate);
-  } else {
-    uint32_t lo = 0, hi = kRqLog10N;  // first j with T[j] > rate
-    while (lo < hi) {
-      const uint32_t m = (lo + hi) >> 1;
-      if (T[m] <= rate) lo = m + 1; else hi = m;
-    }
-    e = kRqLog10Lo + (int32_t)lo - 1;
+  uint32_t lo = 1, hi = kRqLog10N;  // first j with T[j] > rate
+  while (lo < hi) {
+    const uint32_t m = (lo + hi) >> 1;
+    if (T[m] <= rate) lo = m + 1; else hi = m;
   }
-  const uint16_t ex = (uint16_t)e;
+  const uint16_t ex = (uint16_t)(kRqLog10Lo + (int32_t)lo - 1);
   const double p10 = ex < kRqP10N ? r.t[kRqP10 + ex] : __builtin_huge_val();
   const uint16_t mant = (uint16_t)(int32_t)(mulr(4096.0 / 10.0, rate / p10) + 0.5);
   return (uint16_t)((mant << 4) | ex);

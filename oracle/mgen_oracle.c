@@ -1574,6 +1574,57 @@ uint32_t or_log_report_recv(const uint8_t* report, const or_addr* reporter, uint
     return (uint32_t)(p - out);
 }
 
+/* Batch forms of the three calls above (one ctypes call for a whole test).
+ * or_report_build_batch: n reports of one key, row i from v[7 * i ..] = duration, lat_ave,
+ * lat_min, lat_max, rate, loss, offset; the sign flag starts clear in every row.  Item i goes
+ * to items[52 * i ..], its length to len[i]. */
+void or_report_build_batch(const or_addr* src, const or_addr* dst, uint32_t flow_id, int protocol,
+                           uint32_t n, const double* v, uint8_t* items, uint8_t* len)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const double* w = v + 7 * (size_t)i;
+        int sign = 0;
+        len[i] = (uint8_t)or_report_build(src, dst, flow_id, protocol, w[0], w[1], w[2], w[3], w[4],
+                                          w[5], w[6], &sign, items + 52 * (size_t)i);
+    }
+}
+
+/* or_log_report over n rows: item i at items[52 * i ..], row i from v[6 * i ..] = duration,
+ * rate, loss, lat_ave, lat_min, lat_max.  Line i is out[off[i] .. off[i + 1]); every line
+ * needs up to 4096 bytes of out past its start.  Returns off[n]. */
+uint64_t or_log_report_batch(const uint8_t* items, const double* v, const uint64_t* count,
+                             const uint32_t* sec, const uint32_t* usec, uint32_t opts, uint32_t n,
+                             char* out, uint64_t* off)
+{
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const double* w = v + 6 * (size_t)i;
+        off[i] = at;
+        at += or_log_report(items + 52 * (size_t)i, w[0], w[1], w[2], w[3], w[4], w[5], count[i],
+                            sec[i], usec[i], opts, out + at);
+    }
+    off[n] = at;
+    return at;
+}
+
+/* or_log_report_recv over n (record, slab offset) pairs; reporter, sec and usec are per
+ * record, and 52 bytes of slab are readable from every offset.  Lines as above. */
+uint64_t or_log_report_recv_batch(const uint8_t* slab, const uint64_t* pairs,
+                                  const or_addr* reporter, const uint32_t* sec,
+                                  const uint32_t* usec, uint32_t opts, uint32_t n, char* out,
+                                  uint64_t* off)
+{
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t rec = pairs[2 * (size_t)i];
+        off[i] = at;
+        at += or_log_report_recv(slab + pairs[2 * (size_t)i + 1], reporter + rec, sec[rec],
+                                 usec[rec], opts, out + at);
+    }
+    off[n] = at;
+    return at;
+}
+
 /* MgenFlowCommand::GetStatus(flowId) on an item of length len */
 static int flowcmd_status(const uint8_t* b, uint32_t len, uint32_t flow_id)
 {

@@ -281,6 +281,16 @@ uint32_t or_log_report(const uint8_t* report, double duration, double rate, doub
                        uint32_t sec, uint32_t usec, uint32_t opts, char* out);
 uint32_t or_log_report_recv(const uint8_t* report, const or_addr* reporter, uint32_t sec,
                             uint32_t usec, uint32_t opts, char* out);
+void     or_report_build_batch(const or_addr* src, const or_addr* dst, uint32_t flow_id,
+                               int protocol, uint32_t n, const double* v, uint8_t* items,
+                               uint8_t* len);
+uint64_t or_log_report_batch(const uint8_t* items, const double* v, const uint64_t* count,
+                             const uint32_t* sec, const uint32_t* usec, uint32_t opts, uint32_t n,
+                             char* out, uint64_t* off);
+uint64_t or_log_report_recv_batch(const uint8_t* slab, const uint64_t* pairs,
+                                  const or_addr* reporter, const uint32_t* sec,
+                                  const uint32_t* usec, uint32_t opts, uint32_t n, char* out,
+                                  uint64_t* off);
 int      or_data_walk(const uint8_t* pay, uint32_t len, int controller, uint32_t* cmds,
                       uint32_t* n_cmds, uint32_t cap_cmds, uint32_t* reps, uint32_t* n_reps,
                       uint32_t cap_reps);

@@ -485,6 +485,12 @@ def _report_protos():
     L.or_log_report.restype = u32
     L.or_log_report_recv.argtypes = [P, P, u32, u32, u32, P]
     L.or_log_report_recv.restype = u32
+    L.or_report_build_batch.argtypes = [P, P, u32, i32, u32, P, P, P]
+    L.or_report_build_batch.restype = None
+    L.or_log_report_batch.argtypes = [P, P, P, P, P, u32, u32, P, P]
+    L.or_log_report_batch.restype = ctypes.c_uint64
+    L.or_log_report_recv_batch.argtypes = [P, P, P, P, P, u32, u32, P, P]
+    L.or_log_report_recv_batch.restype = ctypes.c_uint64
     L.or_data_walk.argtypes = [P, u32, i32, P, ctypes.POINTER(u32), u32, P, ctypes.POINTER(u32),
                                u32]
     L.or_data_walk.restype = i32
@@ -518,7 +524,7 @@ def log_report(report, duration, rate, loss, lat_ave, lat_min, lat_max, count, s
     L = _report_protos()
     r = np.zeros(52, np.uint8)
     r[:len(report)] = np.frombuffer(report, np.uint8)
-    out = np.zeros(512, np.uint8)
+    out = np.zeros(4096, np.uint8)              # six doubles near 1e308 print about 2 KB
     n = L.or_log_report(_ptr(r), duration, rate, loss, lat_ave, lat_min, lat_max, count, sec,
                         usec, opts, _ptr(out))
     return out[:n].tobytes()
@@ -529,9 +535,60 @@ def log_report_recv(report, reporter, sec, usec, opts=0):
     r = np.zeros(52, np.uint8)
     r[:len(report)] = np.frombuffer(report, np.uint8)
     a = np.ascontiguousarray(np.asarray(reporter, ADDR_DTYPE).reshape(1))
-    out = np.zeros(512, np.uint8)
+    out = np.zeros(4096, np.uint8)
     n = L.or_log_report_recv(_ptr(r), _ptr(a), sec, usec, opts, _ptr(out))
     return out[:n].tobytes()
+
+
+def report_build_batch(src, dst, flow_id, protocol, values):
+    """report_build for every row of values [n x 7] (duration, lat_ave, lat_min, lat_max,
+    rate, loss, offset) with one key and the sign flag clear: (items [n x 52], lengths [n])."""
+    L = _report_protos()
+    s = np.ascontiguousarray(np.asarray(src, ADDR_DTYPE).reshape(1))
+    t = np.ascontiguousarray(np.asarray(dst, ADDR_DTYPE).reshape(1))
+    v = np.ascontiguousarray(values, np.float64).reshape(-1, 7)
+    items = np.zeros((len(v), 52), np.uint8)
+    lens = np.zeros(len(v), np.uint8)
+    L.or_report_build_batch(_ptr(s), _ptr(t), flow_id, protocol, len(v), _ptr(v), _ptr(items),
+                            _ptr(lens))
+    return items, lens
+
+
+def log_report_batch(items, values, count, sec, usec, opts=0, line_cap=4096):
+    """log_report for every row: items [n x 52], values [n x 6] (duration, rate, loss, lat_ave,
+    lat_min, lat_max).  Returns (text bytes, line offsets [n + 1])."""
+    L = _report_protos()
+    it = np.ascontiguousarray(items, np.uint8).reshape(-1, 52)
+    v = np.ascontiguousarray(values, np.float64).reshape(-1, 6)
+    n = len(v)
+    assert len(it) == n
+    c = np.ascontiguousarray(count, np.uint64)
+    s, u = np.ascontiguousarray(sec, np.uint32), np.ascontiguousarray(usec, np.uint32)
+    assert len(c) == len(s) == len(u) == n
+    out = np.zeros((n + 1) * line_cap, np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    total = L.or_log_report_batch(_ptr(it), _ptr(v), _ptr(c), _ptr(s), _ptr(u), opts, n,
+                                  _ptr(out), _ptr(off))
+    return out[:total].tobytes(), off.astype(np.int64)
+
+
+def log_report_recv_batch(slab, pairs, reporter, sec, usec, opts=0, line_cap=512):
+    """log_report_recv for every (record, slab offset) pair; reporter / sec / usec are per
+    record and the slab has 52 readable bytes from every offset.  Returns (text bytes, line
+    offsets [n + 1])."""
+    L = _report_protos()
+    sl = np.ascontiguousarray(slab, np.uint8)
+    p = np.ascontiguousarray(pairs, np.uint64).reshape(-1, 2)
+    n = len(p)
+    assert n == 0 or int(p[:, 1].max()) + 52 <= len(sl)
+    a = np.ascontiguousarray(reporter, ADDR_DTYPE)
+    s, u = np.ascontiguousarray(sec, np.uint32), np.ascontiguousarray(usec, np.uint32)
+    assert n == 0 or int(p[:, 0].max()) < min(len(a), len(s), len(u))
+    out = np.zeros((n + 1) * line_cap, np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    total = L.or_log_report_recv_batch(_ptr(sl), _ptr(p), _ptr(a), _ptr(s), _ptr(u), opts, n,
+                                       _ptr(out), _ptr(off))
+    return out[:total].tobytes(), off.astype(np.int64)
 
 
 def data_walk(payload: bytes, controller=True, cap=4096):

@@ -69,6 +69,8 @@ def test_checker_reads_back_oracle_lines(matrix_text):
 
 
 def _host_parse(tmp_path, buf):
+    if not os.path.exists(HOST):      # as the other tests/cpp programs: built on demand
+        subprocess.run(["make", "-s", "-C", ROOT, "tests/cpp/logparse_host"], check=True)
     assert os.path.exists(HOST), "tests/cpp/logparse_host not built (make all)"
     p = tmp_path / "log.txt"
     p.write_bytes(buf)

@@ -205,6 +205,8 @@ def test_walk_under_sanitizers(oracle, tmp_path):
     """tests/cpp/pcapng_host (address + undefined-behaviour sanitizers): the index over every
     prefix and over single-field mutations of a 40-packet capture with both byte orders'
     worth of block kinds; a sanitizer report exits non-zero."""
+    if not os.path.exists(HOST):      # as the other tests/cpp programs: built on demand
+        subprocess.run(["make", "-s", "-C", ROOT, "tests/cpp/pcapng_host"], check=True)
     assert os.path.exists(HOST), "tests/cpp/pcapng_host not built (make all)"
     f = P.snap(P.capture(oracle, seed=23, n=40), 200)
     for k, swapped in enumerate((False, True)):

@@ -5,6 +5,7 @@ import re
 
 import numpy as np
 
+import report_probe as P
 from report_util import addr, flow_command
 
 
@@ -98,3 +99,103 @@ def test_data_walk_items(oracle):
     assert O.data_walk(bytes(bad))[0] == 2                        # invalid report length
     assert O.data_walk(bytes([0x07, 0, 1]))[0] == 3               # zero length: no progress
     assert O.data_walk(flow_command({45: 1}))[1] == []            # beyond MAX_FLOW
+
+
+# ---- the probe sets of tests/test_gpu_report_numeric.py (report_probe) ----
+def test_probe_doubles_print_as_python_prints_them(oracle):
+    """The two references of the "%lf" test agree: glibc printf (through the oracle's REPORT
+    line) and CPython's "%f" print every finite probe alike; inf and nan carry their sign."""
+    O = oracle
+    vals, count, sec, usec = P.f6_rows()
+    assert 12000 < len(P.f6_values()) < 13000 and len(vals) < 5000
+    rng = np.random.default_rng(2)
+    item, _ = O.report_build(addr(rng, False), addr(rng, False), 7, 1, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    items = np.zeros((len(vals), 52), np.uint8)
+    items[:, :len(item)] = np.frombuffer(item, np.uint8)
+    text, off = O.log_report_batch(items, vals, count, sec, usec)
+    assert int(off[-1]) == len(text) and max(np.diff(off)) > 2000      # past the old 512 bytes
+    nums = re.findall(rb"window>(\S+) rate>(\S+) kbps loss>(\S+) latency ave>(\S+) min>(\S+) "
+                      rb"max>(\S+), count>(\d+)\n", text)
+    assert len(nums) == len(vals)
+    seen = set()
+    for row, c, line in zip(vals, count, nums):
+        assert int(line[6]) == int(c) & 0xFFFFFFFF
+        for k, (v, g) in enumerate(zip(row, line)):
+            v = v * 8e-3 if k == 1 else v
+            if np.isfinite(v):
+                assert g.decode() == P.pct_f(v), (v, g)
+            else:
+                seen.add(g)
+    assert seen == {b"inf", b"-inf", b"nan", b"-nan"}
+    # one row through the single-line entry: the same bytes
+    i = int(np.argmax(np.diff(off)))
+    assert O.log_report(item, *vals[i], int(count[i]), int(sec[i]), int(usec[i])) == \
+        text[off[i]:off[i + 1]]
+
+
+def test_probe_thresholds_are_the_quantizers_steps(oracle):
+    O = oracle
+    thr = P.time_thresholds(O)
+    assert list(thr) == list(range(2, 256))
+    prev = 1e-6
+    for k, t in thr.items():
+        assert t > prev, k
+        assert O.q_time(t) == k and O.q_time(P.step(t, -1)) == k - 1, k
+        prev = t
+    lg = P.log10_thresholds()
+    assert list(lg) == list(range(-323, 309))
+    prev = 0.0
+    for e, t in lg.items():
+        assert t > prev, e
+        assert P.rate_exponent(t) == e, e
+        if e > -323:
+            assert P.rate_exponent(P.step(t, -1)) == e - 1, e
+        prev = t
+    assert lg[-323] == P.DENORM_MIN
+    # the oracle's q_rate takes its exponent from the same log10 (its low 4 bits, 0 <= e < 16)
+    for e in range(1, 16):
+        assert O.q_rate(lg[e]) & 15 == e and O.q_rate(P.step(lg[e], -1)) & 15 == e - 1, e
+
+
+def test_probe_sets_leave_out_what_the_reference_leaves_undefined(oracle):
+    O = oracle
+    tp, rp, lp = P.time_probes(O), P.rate_probes(), P.loss_probes()
+    rows = P.quantizer_rows(O, tp, rp)
+    assert not np.isnan(rows).any()                               # no nan into any quantizer
+    assert np.isfinite(rp).all() and np.isfinite(rows[:, 4]).all()   # no +-inf rate
+    for probes, col in ((tp, 0), (rp, 4), (lp, 5)):
+        assert set(probes.view(np.uint64).tolist()) <= set(rows[:, col].view(np.uint64).tolist())
+    lat = P.latency_plan(tp)
+    assert {tuple(r) for r in lat.view(np.uint64).tolist()} <= \
+        {tuple(r) for r in np.ascontiguousarray(rows[:, 1:4]).view(np.uint64).tolist()}
+    assert np.array_equal(P.loss_code(lp[::64]), [O.q_loss(v) for v in lp[::64]])
+
+
+def test_fused_multiply_add_cannot_move_a_rate_or_loss_code(oracle):
+    """QuantizeRate and QuantizeLoss truncate a * x + 0.5.  Rounding the product first and
+    rounding only the sum (a fused multiply-add) give sums that differ in the last place for
+    some probes, but never on different sides of an integer: for a product of 0.5 or more
+    the addition of 0.5 is exact, or rounds within one binade step far below 1, and a smaller
+    product gives code 0 or 1 either way.  So no probe can tell a contracted multiply from
+    the reference's: shown here in exact rational arithmetic on the probes of both."""
+    from fractions import Fraction
+
+    def sums(a, x):
+        return float(a * x) + 0.5, float(Fraction(a) * Fraction(x) + Fraction(1, 2))
+
+    lp = P.loss_probes()
+    lp = lp[np.isfinite(lp) & (lp != 0.0)]
+    moved = 0
+    for v in np.concatenate([lp[:8], lp[8::8], lp[9::8]]).tolist():
+        u, f = sums(65535.0, v)
+        moved += u != f
+        assert int(min(max(u, 1.0), 65535.0)) == int(min(max(f, 1.0), 65535.0)), v
+        assert int(min(max(u, 1.0), 65535.0)) == oracle.q_loss(v), v
+    rp = P.rate_probes()
+    for v in rp[rp > 0.0][::4].tolist():
+        e = P.rate_exponent(v)
+        if 0 <= e <= 308:
+            u, f = sums(4096.0 / 10.0, v / 10.0 ** e)
+            moved += u != f
+            assert int(u) == int(f), v
+    assert moved > 0                  # the sums do differ: the codes are what cannot
