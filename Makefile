@@ -1,15 +1,18 @@
 # Builds the product library (gfx950), the diagnostics library and the test-only oracle.
-#   mgen_amd/libmgenx.so       product: the C ABI of include/mgenx.h (nothing else exported)
+#   mgen_amd/libmgenx.so       product: the C ABI of include/mgenx.h -- its only C names (mgenx_*);
+#                              the library's internal C++ functions stay visible under their
+#                              mangled names (nothing is built with -fvisibility=hidden)
 #   mgen_amd/libmgenx_diag.so  the same kernels plus the ablation variants and memory probes
 #                              of include/mgenx_diag.h (benchmark scripts only)
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value -Wno-int-to-pointer-cast
-NAMES := mgenx_api mgenx_unpack mgenx_unpack_fixed mgenx_probe \
-         mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_comm mgenx_worker \
-         mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse mgenx_flowdist mgenx_defrag \
-         mgenx_pcap_tcp mgenx_flowseries mgenx_match
+NAMES := mgenx_api mgenx_ctx mgenx_unpack mgenx_unpack_fixed mgenx_probe \
+         mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_binlog mgenx_comm mgenx_worker \
+         mgenx_worker_host mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse \
+         mgenx_flowdist mgenx_defrag mgenx_pcap_tcp mgenx_flowseries mgenx_match
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
+       mgen_amd/csrc/mgenx_internal.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
        mgen_amd/csrc/mgenx_unpack_long.hpp mgen_amd/csrc/mgenx_flowsm.hpp \
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \

@@ -24,7 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 #include "mgenx_flowsm.hpp"
 
 namespace mgenx {
@@ -1302,23 +1302,21 @@ __global__ void flow_export_kernel(const mgenx_flow_state* __restrict__ flows, u
 }  // namespace mgenx
 
 // ------------------------------------------------------------------------------------
-// host side (workspace owned by the context; see mgenx_api.hip)
+// host side (workspace owned by the context: struct mgenx_ctx, mgenx_internal.hpp)
 // ------------------------------------------------------------------------------------
 using namespace mgenx;
 
 struct mgenx_flow_ws {
-  void* mem = nullptr;
-  size_t bytes = 0;
+  DevBuf mem;
   uint32_t cu = 0;  // the device's CU count (the order kernel's persistent grid)
   uint64_t* c1_status = nullptr;  // flow_colscan1_kernel's look-back words (epoch-tagged)
   uint32_t c1_epoch = 0;
 };
 
-extern "C" void* mgenx_flow_ws_new() { return new mgenx_flow_ws(); }
-extern "C" void mgenx_flow_ws_free(void* p) {
-  mgenx_flow_ws* w = static_cast<mgenx_flow_ws*>(p);
+mgenx_flow_ws* mgenx::flow_ws_new() { return new mgenx_flow_ws(); }
+void mgenx::flow_ws_free(mgenx_flow_ws* w) {
   if (!w) return;
-  mgenx::dev_free(w->mem);
+  w->mem.release();
   mgenx::dev_free(w->c1_status);
   delete w;
 }
@@ -1349,8 +1347,8 @@ extern "C" int mgenx_diag_seg_prof(unsigned long long* out, int n) {
 }
 #endif
 
-extern "C" int mgenx_flow_init_run(mgenx_flow_state* flows, uint32_t n_flows, double window,
-                                   hipStream_t stream) {
+int mgenx::flow_init_run(mgenx_flow_state* flows, uint32_t n_flows, double window,
+                         hipStream_t stream) {
   if (!n_flows) return MGENX_OK;
   const uint64_t units = (uint64_t)n_flows * (sizeof(mgenx_flow_state) / 16u);
   hipLaunchKernelGGL(flow_init_kernel, dim3((uint32_t)((units + 255) / 256)), dim3(256), 0, stream, flows,
@@ -1358,24 +1356,27 @@ extern "C" int mgenx_flow_init_run(mgenx_flow_state* flows, uint32_t n_flows, do
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_flow_export_run(const mgenx_flow_state* flows, uint32_t n_flows,
-                                     mgenx_flow_counters* out, hipStream_t stream) {
+int mgenx::flow_export_run(const mgenx_flow_state* flows, uint32_t n_flows,
+                           mgenx_flow_counters* out, hipStream_t stream) {
   if (!n_flows) return MGENX_OK;
   hipLaunchKernelGGL(flow_export_kernel, dim3((n_flows + 255) / 256), dim3(256), 0, stream,
                      flows, n_flows, out);
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+static uint32_t flow_key_bits(uint32_t n_flows) {
+  uint32_t key_bits = 1;
+  while (key_bits < 32 && (1ull << key_bits) <= n_flows) key_bits++;
+  return key_bits;
+}
 
-extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const uint32_t* seq,
-                                     const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
-                                     const mgenx_rec* rows, const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
-                                     mgenx_flow_state* flows, uint32_t n_flows,
-                                     mgenx_flow_report* reports, uint32_t per_flow,
-                                     uint32_t* report_count, uint32_t* report_rec,
-                                     hipStream_t stream, char* err, size_t errn) {
-  mgenx_flow_ws& ws = *static_cast<mgenx_flow_ws*>(wsp);
+int mgenx::flow_reduce_run(mgenx_flow_ws* wsp, const uint32_t* flow_idx, const uint32_t* seq,
+                           const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                           const mgenx_rec* rows, const uint32_t* rxs, const uint32_t* rxu,
+                           uint32_t n, mgenx_flow_state* flows, uint32_t n_flows,
+                           mgenx_flow_report* reports, uint32_t per_flow, uint32_t* report_count,
+                           uint32_t* report_rec, hipStream_t stream, char* err, size_t errn) {
+  mgenx_flow_ws& ws = *wsp;
   if (n == 0 || n_flows == 0) return MGENX_OK;
   const RecSrc src = {seq, txs, txu, len, rows, rxs, rxu};
   int sort_path = (uint64_t)n_flows + 1 <= kCountBins ? 0 : 1;  // 0 counting, 1 radix
@@ -1387,8 +1388,7 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
   if (const char* sw = getenv("MGENX_AN_SEQW")) oseqw = (uint32_t)atoi(sw);
 #endif
   const uint32_t bins = n_flows + 1u;
-  uint32_t key_bits = 1;
-  while (key_bits < 32 && (1ull << key_bits) <= n_flows) key_bits++;
+  const uint32_t key_bits = flow_key_bits(n_flows);
   // persistent order grid: one block per CU (LDS allows one), a multiple of 8 (one set per XCD)
   if (!ws.cu) {
     int dev = 0, cu = 0;
@@ -1430,30 +1430,22 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
   const size_t common = rb + lb + cb;
   const size_t need = common + (sort_path == 0 ? 2 * hb + (want_order ? nb : 0) + a256(cub_bytes)
                                                : 4 * nb + bb + a256(cub_bytes));
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "flow_reduce: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  if (ws.mem.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "flow_reduce: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  char* p = static_cast<char*>(ws.mem);
-  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  Carve take(ws.mem.p);
   FRec* recs = (FRec*)take(rb);
   double* lat2 = (double*)take(lb);
   CloseRec* closes = (CloseRec*)take(cb);
   const uint32_t* bnd;
-  uint32_t bstride;
   uint32_t* order = nullptr;
   hipError_t e;
   if (sort_path == 0) {
     uint32_t* hist = (uint32_t*)take(hb);
     uint32_t* start = (uint32_t*)take(hb);
     if (want_order) order = (uint32_t*)take(nb);
-    uint32_t* totals = (uint32_t*)take(a256(cub_bytes));
+    uint32_t* totals = (uint32_t*)take(cub_bytes);
     hipLaunchKernelGGL(flow_hist_kernel, dim3(n_tiles), dim3(512), bins * 4u, stream, flow_idx, n,
                        n_flows, tile, hist);
     // the single-pass scan (flow_colscan1_kernel) up to 512 tiles: each of its blocks reads
@@ -1515,14 +1507,13 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
       return MGENX_EDEVICE;
     }
     bnd = start;  // tile 0's row: flow k starts at start[k]
-    bstride = 1;
   } else {
     uint32_t* keys_in = (uint32_t*)take(nb);
     uint32_t* keys_out = (uint32_t*)take(nb);
     uint32_t* vals_in = (uint32_t*)take(nb);
     order = (uint32_t*)take(nb);
     uint32_t* d_bnd = (uint32_t*)take(bb);
-    void* cub_tmp = take(a256(cub_bytes));
+    void* cub_tmp = take(cub_bytes);
     hipLaunchKernelGGL(flow_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, flow_idx, n,
                        n_flows, keys_in, vals_in);
     e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_in, keys_out, vals_in, order,
@@ -1536,11 +1527,11 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
     hipLaunchKernelGGL(flow_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, order,
                        d_bnd, n_flows, src, recs);
     bnd = d_bnd;
-    bstride = 1;
   }
   if (sabl) return MGENX_OK;  // timing study: ordering only
+  // (bnd's stride is 1 on both paths; the kernel keeps its parameter)
   hipLaunchKernelGGL(flow_update_kernel, dim3((n_flows + 3) / 4), dim3(256), 0, stream, flows,
-                     n_flows, bnd, bstride, recs, order, lat2, reports, per_flow, report_count,
+                     n_flows, bnd, 1u, recs, order, lat2, reports, per_flow, report_count,
                      report_rec, closes, n);
   e = hipGetLastError();
   if (e != hipSuccess) {
@@ -1552,15 +1543,9 @@ extern "C" int mgenx_flow_reduce_run(void* wsp, const uint32_t* flow_idx, const 
 
 // The radix ordering alone, for mgenx_flow_dist (mgenx_flowdist.hip): flow_keys_kernel, the
 // stable pair sort and flow_bounds_kernel as the radix path above runs them.  `mem` holds
-// mgenx_flow_sort_ws(n, n_flows) bytes.  keys[p] = the flow of sorted position p (n_flows for a
+// mgenx::flow_sort_ws(n, n_flows) bytes.  keys[p] = the flow of sorted position p (n_flows for a
 // skipped record), order[p] = its record, bnd[f] = the first position with flow >= f
 // (f = 0..n_flows).
-static uint32_t flow_key_bits(uint32_t n_flows) {
-  uint32_t key_bits = 1;
-  while (key_bits < 32 && (1ull << key_bits) <= n_flows) key_bits++;
-  return key_bits;
-}
-
 static size_t flow_sort_cub_bytes(uint32_t n, uint32_t n_flows) {
   size_t cub_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const uint32_t*)nullptr,
@@ -1570,25 +1555,23 @@ static size_t flow_sort_cub_bytes(uint32_t n, uint32_t n_flows) {
   return cub_bytes;
 }
 
-extern "C" size_t mgenx_flow_sort_ws(uint32_t n, uint32_t n_flows) {
+size_t mgenx::flow_sort_ws(uint32_t n, uint32_t n_flows) {
   return 4 * a256((size_t)n * 4) + a256(((size_t)n_flows + 1) * 4) +
          a256(flow_sort_cub_bytes(n, n_flows));
 }
 
-extern "C" int mgenx_flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n,
-                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
-                                   const uint32_t** bnd, hipStream_t stream, char* err,
-                                   size_t errn) {
+int mgenx::flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n, uint32_t n_flows,
+                         const uint32_t** keys, const uint32_t** order, const uint32_t** bnd,
+                         hipStream_t stream, char* err, size_t errn) {
   const size_t nb = a256((size_t)n * 4), bb = a256(((size_t)n_flows + 1) * 4);
   size_t cub_bytes = flow_sort_cub_bytes(n, n_flows);
-  char* p = static_cast<char*>(mem);
-  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  Carve take(mem);
   uint32_t* keys_in = (uint32_t*)take(nb);
   uint32_t* keys_out = (uint32_t*)take(nb);
   uint32_t* vals_in = (uint32_t*)take(nb);
   uint32_t* vals_out = (uint32_t*)take(nb);
   uint32_t* d_bnd = (uint32_t*)take(bb);
-  void* cub_tmp = take(a256(cub_bytes));
+  void* cub_tmp = take(cub_bytes);
   hipLaunchKernelGGL(flow_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, flow_idx, n,
                      n_flows, keys_in, vals_in);
   hipError_t e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_in, keys_out, vals_in,

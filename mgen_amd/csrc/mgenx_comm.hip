@@ -13,14 +13,13 @@
 
 #include <rccl/rccl.h>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx.h"
+#include "mgenx_internal.hpp"
 
 struct mgenx_comm {
   ncclComm_t comm = nullptr;
   int nranks = 0, rank = 0, device = 0;
 };
-
-extern "C" int mgenx_ctx_device(const mgenx_ctx* ctx);
 
 extern "C" {
 

@@ -26,7 +26,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "mgenx_capture.hpp"
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 namespace defrag {
@@ -329,8 +329,6 @@ __global__ void __launch_bounds__(256) defrag_gather_kernel(Params p) {
   }
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static size_t cub_bytes(uint32_t n) {
   size_t a = 0, b = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint64_t*)nullptr,
@@ -345,8 +343,10 @@ static size_t cub_bytes(uint32_t n) {
 }  // namespace mgenx
 
 using namespace mgenx::defrag;
+using mgenx::a256;
+using mgenx::Carve;
 
-extern "C" size_t mgenx_defrag_ws(uint32_t n) {
+static size_t defrag_ws(uint32_t n) {
   const size_t N = n;
   return 4 * a256(N * 8) + a256(N * 32) + 4 * a256(N * 4) + 2 * a256(N) +
          a256((N + kCntN) * 8) + a256(cub_bytes(n));
@@ -354,16 +354,14 @@ extern "C" size_t mgenx_defrag_ws(uint32_t n) {
 
 // dev_data_off null: classic records at dev_pkt_off; else pcapng, dev_pkt_off = the packet
 // blocks and dev_data_off / dev_cap_len what mgenx_pcapng_parse wrote.  `mem` holds
-// mgenx_defrag_ws(n) bytes.  Synchronizes the stream once (the sizes' read-back).
-extern "C" int mgenx_defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off,
-                                uint64_t buf_bytes, const uint64_t* dev_pkt_off,
-                                const uint64_t* dev_data_off, const uint32_t* dev_cap_len,
-                                uint32_t n, uint32_t link_type, uint32_t flags,
-                                int64_t timeout_us, const uint32_t* dev_rx_sec,
-                                const uint32_t* dev_rx_usec, uint8_t* dev_status,
-                                uint64_t* dev_udp_off, uint32_t* dev_udp_len, mgenx_addr* dev_src,
-                                mgenx_defrag_stats* stats, hipStream_t stream, char* err,
-                                size_t errn) {
+// defrag_ws(n) bytes.  Synchronizes the stream once (the sizes' read-back).
+static int defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                      const uint64_t* dev_pkt_off, const uint64_t* dev_data_off,
+                      const uint32_t* dev_cap_len, uint32_t n, uint32_t link_type, uint32_t flags,
+                      int64_t timeout_us, const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      mgenx_addr* dev_src, mgenx_defrag_stats* stats, hipStream_t stream, char* err,
+                      size_t errn) {
   Params p;
   p.buf = dev_buf; p.limit = scratch_off; p.buf_bytes = buf_bytes; p.scratch_off = scratch_off;
   p.pkt_off = dev_pkt_off; p.data_off = dev_data_off; p.cap_len = dev_cap_len; p.n = n;
@@ -371,8 +369,7 @@ extern "C" int mgenx_defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_of
   p.rx_sec = dev_rx_sec; p.rx_usec = dev_rx_usec; p.status = dev_status;
   p.udp_off = dev_udp_off; p.udp_len = dev_udp_len; p.src = dev_src;
   const size_t N = n;
-  char* m = static_cast<char*>(mem);
-  auto take = [&](size_t b) { char* q = m; m += a256(b); return q; };
+  Carve take(mem);
   p.hash_in = (uint64_t*)take(N * 8);
   p.hash_out = (uint64_t*)take(N * 8);
   p.meta = (uint64_t*)take(N * 8);
@@ -423,3 +420,56 @@ extern "C" int mgenx_defrag_run(void* mem, uint8_t* dev_buf, uint64_t scratch_of
   e = hipGetLastError();
   return e == hipSuccess ? MGENX_OK : fail(e, "pcap_defrag");
 }
+
+// ---- the C ABI of the defrag step ----
+using mgenx::set_err;
+
+extern "C" {
+
+// both defrags: dev_data_off null = classic records at dev_pkt_off, else pcapng packet blocks
+static int pcap_defrag_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                           uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                           const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                           uint32_t link_type, uint32_t flags, int64_t timeout_us,
+                           const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                           uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                           mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  if (!ctx || !stats || buf_bytes < scratch_off || n > 0x7FFFFFFEu) return MGENX_EINVAL;
+  memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_rx_sec || !dev_rx_usec || !dev_status || !dev_udp_off ||
+      !dev_udp_len || !dev_src)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  void* m = ctx->defrag.get(defrag_ws(n));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_defrag workspace");
+  return defrag_run(m, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                          dev_cap_len, n, link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec,
+                          dev_status, dev_udp_off, dev_udp_len, dev_src, stats,
+                          (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_pcap_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                      const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                      int64_t timeout_us, const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  return pcap_defrag_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, nullptr, nullptr, n,
+                         link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec, dev_status,
+                         dev_udp_off, dev_udp_len, dev_src, stats, stream);
+}
+
+int mgenx_pcapng_defrag(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                        uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                        const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                        uint32_t link_type, uint32_t flags, int64_t timeout_us,
+                        const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec,
+                        uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                        mgenx_addr* dev_src, mgenx_defrag_stats* stats, void* stream) {
+  if (n && (!dev_data_off || !dev_cap_len)) return MGENX_EINVAL;
+  return pcap_defrag_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                         dev_cap_len, n, link_type, flags, timeout_us, dev_rx_sec, dev_rx_usec,
+                         dev_status, dev_udp_off, dev_udp_len, dev_src, stats, stream);
+}
+
+}  // extern "C"

@@ -7,7 +7,7 @@
 // numbers.  So:
 //   0. flow_dist_snap_kernel copies what the batch's first record of a flow pairs with
 //      (last_lat, last_rx, seq_max) out of the states, which the main pass updates in place;
-//   1. the records are ordered by flow, stably (mgenx_flow_sort_run: flow_reduce's radix path),
+//   1. the records are ordered by flow, stably (mgenx::flow_sort_run: flow_reduce's radix path),
 //      and flow_dist_pack_kernel writes each record's latency, receive time, seq and length as
 //      one 32-B record, so that the passes below gather one line per record, not six;
 //   2. the sorted positions are cut into chunks of kChunk, whatever the flow edges are: one
@@ -21,7 +21,7 @@
 //      histogram and a workgroup reduction flushed with one atomic per field and non-zero bin,
 //      or (shorter runs) atomics straight from the lanes.  Sums, minima and maxima of integers
 //      commute, so the bytes left do not depend on the order the workgroups finish in.
-// Passes 1 and 2 are mgenx_flow_prep_run, which mgenx_flow_series (mgenx_flowseries.hip) runs too;
+// Passes 1 and 2 are mgenx::flow_prep_run, which mgenx_flow_series (mgenx_flowseries.hip) runs too;
 // what both main passes use of them (DistRec, block_segmax, kChunk) is in mgenx_flowdist.hpp.
 #include <hip/hip_runtime.h>
 
@@ -29,7 +29,7 @@
 #include <stdio.h>
 
 #include "mgenx_flowdist.hpp"
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -442,31 +442,13 @@ __global__ void flow_dist_quantiles_kernel(const DistState* __restrict__ dist,
 }  // namespace mgenx
 
 // ------------------------------------------------------------------------------------
-// host side (workspace owned by the context; see mgenx_api.hip)
+// host side (workspace owned by the context: struct mgenx_ctx, mgenx_internal.hpp)
 // ------------------------------------------------------------------------------------
 using namespace mgenx;
 
-extern "C" size_t mgenx_flow_sort_ws(uint32_t n, uint32_t n_flows);
-extern "C" int mgenx_flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n,
-                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
-                                   const uint32_t** bnd, hipStream_t stream, char* err,
-                                   size_t errn);
 
-struct mgenx_flowdist_ws {
-  void* mem = nullptr;
-  size_t bytes = 0;
-};
-
-extern "C" void* mgenx_flowdist_ws_new() { return new mgenx_flowdist_ws(); }
-extern "C" void mgenx_flowdist_ws_free(void* p) {
-  mgenx_flowdist_ws* w = static_cast<mgenx_flowdist_ws*>(p);
-  if (!w) return;
-  mgenx::dev_free(w->mem);
-  delete w;
-}
-
-extern "C" int mgenx_flow_dist_init_run(DistState* dist, uint64_t* hist, uint32_t n_flows,
-                                        hipStream_t stream) {
+int mgenx::flow_dist_init_run(struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
+                              hipStream_t stream) {
   if (!n_flows) return MGENX_OK;
   hipLaunchKernelGGL(flow_dist_init_kernel, dim3((n_flows + 255u) / 256u), dim3(256), 0, stream,
                      dist, n_flows);
@@ -477,32 +459,28 @@ extern "C" int mgenx_flow_dist_init_run(DistState* dist, uint64_t* hist, uint32_
   return MGENX_OK;
 }
 
-static size_t fd_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the passes mgenx_flow_dist and mgenx_flow_series share (mgenx_flowdist.hpp)
-extern "C" size_t mgenx_flow_prep_ws(uint32_t n, uint32_t n_flows) {
+size_t mgenx::flow_prep_ws(uint32_t n, uint32_t n_flows) {
   const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
-  return fd_a256(mgenx_flow_sort_ws(n, n_flows)) + 2 * fd_a256((size_t)n_chunks * 8u) +
-         fd_a256((size_t)n_chunks * 4u) + fd_a256((size_t)n * sizeof(DistRec));
+  return a256(mgenx::flow_sort_ws(n, n_flows)) + 2 * a256((size_t)n_chunks * 8u) +
+         a256((size_t)n_chunks * 4u) + a256((size_t)n * sizeof(DistRec));
 }
 
-extern "C" int mgenx_flow_prep_run(void* mem, const uint32_t* flow_idx, const uint32_t* seq,
-                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
-                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
-                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
-                                   const uint32_t** bnd, const DistRec** rec_out,
-                                   const int64_t** scan_out, hipStream_t stream, char* err,
-                                   size_t errn) {
+int mgenx::flow_prep_run(void* mem, const uint32_t* flow_idx, const uint32_t* seq,
+                         const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                         const uint32_t* rxs, const uint32_t* rxu, uint32_t n, uint32_t n_flows,
+                         const uint32_t** keys, const uint32_t** order, const uint32_t** bnd,
+                         const DistRec** rec_out, const int64_t** scan_out, hipStream_t stream,
+                         char* err, size_t errn) {
   const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
-  const size_t c8 = fd_a256((size_t)n_chunks * 8u), c4 = fd_a256((size_t)n_chunks * 4u);
-  char* p = static_cast<char*>(mem);
-  auto take = [&](size_t b) { char* q = p; p += b; return q; };
-  void* sort_mem = take(fd_a256(mgenx_flow_sort_ws(n, n_flows)));
+  const size_t c8 = a256((size_t)n_chunks * 8u), c4 = a256((size_t)n_chunks * 4u);
+  Carve take(mem);
+  void* sort_mem = take(mgenx::flow_sort_ws(n, n_flows));
   int64_t* tail_max = (int64_t*)take(c8);
   int64_t* scan = (int64_t*)take(c8);
   uint32_t* tail_cont = (uint32_t*)take(c4);
-  DistRec* rec = (DistRec*)take(fd_a256((size_t)n * sizeof(DistRec)));
-  const int rc = mgenx_flow_sort_run(sort_mem, flow_idx, n, n_flows, keys, order, bnd, stream, err,
+  DistRec* rec = (DistRec*)take((size_t)n * sizeof(DistRec));
+  const int rc = mgenx::flow_sort_run(sort_mem, flow_idx, n, n_flows, keys, order, bnd, stream, err,
                                      errn);
   if (rc != MGENX_OK) return rc;
   const DistCols col = {seq, txs, txu, len, rxs, rxu};
@@ -517,33 +495,26 @@ extern "C" int mgenx_flow_prep_run(void* mem, const uint32_t* flow_idx, const ui
   return MGENX_OK;
 }
 
-extern "C" int mgenx_flow_dist_run(void* wsp, const uint32_t* flow_idx, const uint32_t* seq,
-                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
-                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
-                                   DistState* dist, uint64_t* hist, uint32_t n_flows,
-                                   hipStream_t stream, char* err, size_t errn) {
-  mgenx_flowdist_ws& ws = *static_cast<mgenx_flowdist_ws*>(wsp);
+int mgenx::flow_dist_run(DevBuf& ws, const uint32_t* flow_idx, const uint32_t* seq,
+                         const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                         const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                         struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
+                         hipStream_t stream, char* err, size_t errn) {
   if (n == 0 || n_flows == 0) return MGENX_OK;
   const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
-  const size_t snap_b = fd_a256((size_t)n_flows * sizeof(DistSnap));
-  const size_t need = snap_b + mgenx_flow_prep_ws(n, n_flows);
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "flow_dist: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  const size_t snap_b = a256((size_t)n_flows * sizeof(DistSnap));
+  const size_t need = snap_b + mgenx::flow_prep_ws(n, n_flows);
+  if (ws.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "flow_dist: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  DistSnap* snap = (DistSnap*)ws.mem;
+  DistSnap* snap = (DistSnap*)ws.p;
   hipLaunchKernelGGL(flow_dist_snap_kernel, dim3((n_flows + 255u) / 256u), dim3(256), 0, stream,
                      dist, n_flows, snap);
   const uint32_t *keys, *order, *bnd;
   const DistRec* rec;
   const int64_t* scan;
-  const int rc = mgenx_flow_prep_run(static_cast<char*>(ws.mem) + snap_b, flow_idx, seq, txs, txu,
+  const int rc = mgenx::flow_prep_run(static_cast<char*>(ws.p) + snap_b, flow_idx, seq, txs, txu,
                                      len, rxs, rxu, n, n_flows, &keys, &order, &bnd, &rec, &scan,
                                      stream, err, errn);
   if (rc != MGENX_OK) return rc;
@@ -561,9 +532,9 @@ extern "C" int mgenx_flow_dist_run(void* wsp, const uint32_t* flow_idx, const ui
   return MGENX_OK;
 }
 
-extern "C" int mgenx_flow_dist_quantiles_run(const DistState* dist, const uint64_t* hist,
-                                             uint32_t n_flows, const uint32_t* permille,
-                                             uint32_t n_q, int64_t* out, hipStream_t stream) {
+int mgenx::flow_dist_quantiles_run(const struct mgenx_flow_dist* dist, const uint64_t* hist,
+                                   uint32_t n_flows, const uint32_t* permille, uint32_t n_q,
+                                   int64_t* out, hipStream_t stream) {
   for (uint32_t q0 = 0; q0 < n_q; q0 += kQGroup) {
     DistQ qs = {};
     const uint32_t cnt = n_q - q0 < kQGroup ? n_q - q0 : kQGroup;

@@ -1,7 +1,8 @@
 // The latency histogram's bin arithmetic (mgenx_flow_dist): one definition for the kernels and
 // the exported host functions mgenx_flow_dist_bin / mgenx_flow_dist_bin_lo.  Below it, what
-// mgenx_flow_dist and mgenx_flow_series share: the chunk size, the packed record, the segmented
-// max scan and the sort / pack / carry passes behind mgenx_flow_prep_run.
+// mgenx_flow_dist and mgenx_flow_series share: the chunk size, the packed record and the
+// segmented max scan of the sort / pack / carry passes behind mgenx::flow_prep_run
+// (mgenx_flowdist.hip; declared in mgenx_internal.hpp).
 //
 // 0 <= v < 2^32 microseconds in MGENX_FLOW_DIST_BINS = 896 bins: one bin per value below 64, then
 // 32 sub-bins per octave (a relative width of 1/32 .. 1/64):
@@ -107,19 +108,3 @@ __device__ __forceinline__ int64_t block_segmax(int64_t v, bool head, int64_t* s
 #endif
 
 }  // namespace mgenx
-
-// The passes mgenx_flow_dist and mgenx_flow_series share (mgenx_flowdist.hip): the stable sort
-// by flow (keys / order / bnd as mgenx_flow_sort_run leaves them), the packed records rec[i] of
-// the input order, and scan[c], the largest seq of chunk c's last flow over chunk c and the
-// chunks before it that this flow fills.  mem: mgenx_flow_prep_ws(n, n_flows) bytes of device
-// memory, 256-B aligned; n, n_flows >= 1.
-#if defined(__HIPCC__)
-extern "C" size_t mgenx_flow_prep_ws(uint32_t n, uint32_t n_flows);
-extern "C" int mgenx_flow_prep_run(void* mem, const uint32_t* flow_idx, const uint32_t* seq,
-                                   const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
-                                   const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
-                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
-                                   const uint32_t** bnd, const mgenx::DistRec** rec,
-                                   const int64_t** scan, hipStream_t stream, char* err,
-                                   size_t errn);
-#endif

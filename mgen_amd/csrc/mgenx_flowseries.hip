@@ -5,7 +5,7 @@
 // Ordered by flow with the receive order kept, a record needs its predecessor in the flow (the
 // jitter) and the running maximum M of the flow's earlier sequence numbers (fresh / late /
 // advance); everything else is the record's own.  The first passes are mgenx_flow_dist's
-// (mgenx_flow_prep_run, mgenx_flowdist.hip): the stable sort by flow, one 32-B record per input
+// (mgenx::flow_prep_run, mgenx_flowdist.hip): the stable sort by flow, one 32-B record per input
 // record, and per chunk of kChunk sorted positions the M its first run starts from.  Then:
 //   0. flow_series_snap_kernel copies what the batch's first record of a flow pairs with
 //      (n, last_lat, seq_max) out of the states, which the main pass overwrites;
@@ -25,7 +25,7 @@
 #include <stdio.h>
 
 #include "mgenx_flowdist.hpp"
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -268,26 +268,14 @@ flow_series_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __res
 }  // namespace mgenx
 
 // ------------------------------------------------------------------------------------
-// host side (workspace owned by the context; see mgenx_api.hip)
+// host side (workspace owned by the context: struct mgenx_ctx, mgenx_internal.hpp)
 // ------------------------------------------------------------------------------------
 using namespace mgenx;
 
-struct mgenx_flowseries_ws {
-  void* mem = nullptr;
-  size_t bytes = 0;
-};
-
-extern "C" void* mgenx_flowseries_ws_new() { return new mgenx_flowseries_ws(); }
-extern "C" void mgenx_flowseries_ws_free(void* p) {
-  mgenx_flowseries_ws* w = static_cast<mgenx_flowseries_ws*>(p);
-  if (!w) return;
-  mgenx::dev_free(w->mem);
-  delete w;
-}
-
 // n_flows >= 1, n_flows * n_bins < 2^31
-extern "C" int mgenx_flow_series_init_run(SeriesState* state, SeriesBin* bins, uint32_t n_flows,
-                                          uint32_t n_bins, hipStream_t stream) {
+int mgenx::flow_series_init_run(struct mgenx_flow_series_state* state,
+                                struct mgenx_flow_series_bin* bins, uint32_t n_flows,
+                                uint32_t n_bins, hipStream_t stream) {
   const uint32_t n_cells = n_flows * n_bins;
   const uint32_t m = n_cells > n_flows ? n_cells : n_flows;
   hipLaunchKernelGGL(flow_series_init_kernel, dim3((m + 255u) / 256u), dim3(256), 0, stream, state,
@@ -295,33 +283,26 @@ extern "C" int mgenx_flow_series_init_run(SeriesState* state, SeriesBin* bins, u
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_flow_series_run(void* wsp, const uint32_t* flow_idx, const uint32_t* seq,
-                                     const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
-                                     const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
-                                     int64_t t0, uint64_t width, uint32_t n_bins,
-                                     SeriesState* state, SeriesBin* bins, uint32_t n_flows,
-                                     hipStream_t stream, char* err, size_t errn) {
-  mgenx_flowseries_ws& ws = *static_cast<mgenx_flowseries_ws*>(wsp);
+int mgenx::flow_series_run(DevBuf& ws, const uint32_t* flow_idx, const uint32_t* seq,
+                           const uint32_t* txs, const uint32_t* txu, const uint16_t* len,
+                           const uint32_t* rxs, const uint32_t* rxu, uint32_t n, int64_t t0,
+                           uint64_t width, uint32_t n_bins, struct mgenx_flow_series_state* state,
+                           struct mgenx_flow_series_bin* bins, uint32_t n_flows, hipStream_t stream,
+                           char* err, size_t errn) {
   const uint32_t n_chunks = (n + kChunk - 1u) / kChunk;
-  const size_t snap_b = ((size_t)n_flows * sizeof(SeriesSnap) + 255) & ~(size_t)255;
-  const size_t need = snap_b + mgenx_flow_prep_ws(n, n_flows);
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "flow_series: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  const size_t snap_b = a256((size_t)n_flows * sizeof(SeriesSnap));
+  const size_t need = snap_b + mgenx::flow_prep_ws(n, n_flows);
+  if (ws.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "flow_series: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  SeriesSnap* snap = (SeriesSnap*)ws.mem;
+  SeriesSnap* snap = (SeriesSnap*)ws.p;
   hipLaunchKernelGGL(flow_series_snap_kernel, dim3((n_flows + 255u) / 256u), dim3(256), 0, stream,
                      state, n_flows, snap);
   const uint32_t *keys, *order, *bnd;
   const DistRec* rec;
   const int64_t* scan;
-  const int rc = mgenx_flow_prep_run(static_cast<char*>(ws.mem) + snap_b, flow_idx, seq, txs, txu,
+  const int rc = mgenx::flow_prep_run(static_cast<char*>(ws.p) + snap_b, flow_idx, seq, txs, txu,
                                      len, rxs, rxu, n, n_flows, &keys, &order, &bnd, &rec, &scan,
                                      stream, err, errn);
   if (rc != MGENX_OK) return rc;

@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <string.h>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -621,8 +621,7 @@ struct mgenx_flow_table {
                                  // created (alternate calls)
   uint32_t parity = 0;
   int cu = 256;              // compute units (the small-table path's grid)
-  void* ws = nullptr;        // per-call scratch: rec_slot, flag, pos, cub temp
-  size_t ws_bytes = 0;
+  DevBuf ws;                 // per-call scratch: rec_slot, flag, blk_cnt, blk_base
 };
 
 extern "C" {
@@ -654,7 +653,7 @@ int mgenx_flow_table_destroy(mgenx_flow_table* t) {
   if (!t) return MGENX_EINVAL;
   mgenx::dev_free(t->slots);
   mgenx::dev_free(t->counters);
-  mgenx::dev_free(t->ws);
+  t->ws.release();
   delete t;
   return MGENX_OK;
 }
@@ -669,20 +668,13 @@ int mgenx_flow_lookup(mgenx_ctx* ctx, mgenx_flow_table* t, const mgenx_cols* col
   if (!dev_src || !dev_flow_idx) return MGENX_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const uint32_t nblk = (n + kFtBlock - 1) / kFtBlock;
-  const size_t nb = ((size_t)n * 4 + 255) & ~(size_t)255;
-  const size_t bb = ((size_t)nblk * 4 + 255) & ~(size_t)255;
-  const size_t need = 2 * nb + 2 * bb + 256;
-  if (t->ws_bytes < need) {
-    mgenx::dev_free(t->ws);
-    t->ws = nullptr;
-    t->ws_bytes = 0;
-    if (hipMalloc(&t->ws, need) != hipSuccess) return MGENX_ENOMEM;
-    t->ws_bytes = need;
-  }
-  uint32_t* rec_slot = (uint32_t*)t->ws;
-  uint32_t* flag = (uint32_t*)((char*)t->ws + nb);
-  uint32_t* blk_cnt = (uint32_t*)((char*)t->ws + 2 * nb);
-  uint32_t* blk_base = (uint32_t*)((char*)t->ws + 2 * nb + bb);
+  const size_t nb = a256((size_t)n * 4), bb = a256((size_t)nblk * 4);
+  if (t->ws.reserve(2 * nb + 2 * bb + 256) != hipSuccess) return MGENX_ENOMEM;
+  Carve take(t->ws.p);
+  uint32_t* rec_slot = (uint32_t*)take(nb);
+  uint32_t* flag = (uint32_t*)take(nb);
+  uint32_t* blk_cnt = (uint32_t*)take(bb);
+  uint32_t* blk_base = (uint32_t*)take(bb);
   // n_new alternates between counters[3] and [4]: each call clears the word the next call
   // counts in
   uint32_t* n_new = t->counters + 3 + (t->parity & 1u);

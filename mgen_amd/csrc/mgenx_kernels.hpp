@@ -1,4 +1,7 @@
-// mgenx_kernels.hpp -- kernel parameter blocks and launchers shared with mgenx_api.hip.
+// mgenx_kernels.hpp -- what it takes to launch another file's kernel: the parameter blocks, the
+// launch_* functions and the layouts host and device agree on (the worker's mailbox, the report
+// quantizer tables kRq*, the operator tables kTab*).  Host-only code shared between the files
+// (the context, the growing device buffer, the *_run functions) is in mgenx_internal.hpp.
 #pragma once
 
 #include "mgenx_common.hpp"
@@ -12,24 +15,6 @@
 #endif
 
 namespace mgenx {
-
-// Ends the resident worker waves (mgenx_worker_*, mgenx_api.hip) of `device` (every device when
-// device < 0) and waits for them; the calling thread's current device is left as it was.
-// hipFree / hipHostFree synchronise the device, so with a wave still polling its mailbox they
-// would wait for its idle timeout: every workspace growth frees through these.
-void quiesce_workers(int device);
-inline void dev_free(void* p) {
-  if (!p) return;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  quiesce_workers(dev);  // hipFree synchronises the current device only
-  (void)hipFree(p);
-}
-inline void host_free(void* p) {
-  if (!p) return;
-  quiesce_workers(-1);  // pinned host memory may be mapped on every device
-  (void)hipHostFree(p);
-}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is
 // per device, and threaded multi-GPU callers (mgenx::ShardedScan) launch concurrently, so the
@@ -194,7 +179,7 @@ struct alignas(64) WRep {
 };
 static_assert(sizeof(WPackReq) <= kPollData, "Pack's request travels in the polled pieces");
 static_assert(sizeof(WUpdReq) <= kPollData, "Update's request travels in the polled pieces");
-// the context's operator tables (mgenx_api.hip: A_n(s) = the state after n zero bytes, as 4 x 256
+// the context's operator tables (mgenx_ctx.hip: A_n(s) = the state after n zero bytes, as 4 x 256
 // byte-indexed entries): [A64 | A4 | A8 | A12 | A16 | A32 | A48 | A128 | A256 | A512 | A1024]
 constexpr uint32_t kTabA64 = 0, kTabA4 = 1, kTabA8 = 2, kTabA16 = 4, kTabA32 = 5, kTabA128 = 7,
                    kTabA256 = 8, kTabA512 = 9, kTabA1024 = 10, kTabCount = 11;

@@ -20,7 +20,7 @@
 
 #include <mutex>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -430,28 +430,25 @@ using namespace mgenx;
 // but different streams never share a buffer; an area grows (hipMalloc) only when a batch
 // outgrows it.
 struct mgenx_log_ws {
-  void* mem = nullptr;
-  size_t bytes = 0;
+  DevBuf mem;
   hipStream_t stream = nullptr;
   mgenx_log_ws* next = nullptr;
 };
 
-extern "C" void* mgenx_log_ws_new() { return new mgenx_log_ws(); }
-extern "C" void mgenx_log_ws_free(void* p) {
-  mgenx_log_ws* w = static_cast<mgenx_log_ws*>(p);
+mgenx_log_ws* mgenx::log_ws_new() { return new mgenx_log_ws(); }
+void mgenx::log_ws_free(mgenx_log_ws* w) {
   while (w) {
     mgenx_log_ws* nx = w->next;
-    mgenx::dev_free(w->mem);
+    w->mem.release();
     delete w;
     w = nx;
   }
 }
 // the area of `stream` (the head is the first stream's; others are chained)
-static mgenx_log_ws& ws_for(void* wsp, hipStream_t stream) {
+static mgenx_log_ws& ws_for(mgenx_log_ws* head, hipStream_t stream) {
   static std::mutex mu;  // the chain is shared by the context's host threads
   std::lock_guard<std::mutex> lock(mu);
-  mgenx_log_ws* head = static_cast<mgenx_log_ws*>(wsp);
-  if (!head->mem && !head->next && head->bytes == 0) head->stream = stream;
+  if (!head->mem.p && !head->next && head->mem.bytes == 0) head->stream = stream;
   for (mgenx_log_ws* w = head; w; w = w->next)
     if (w->stream == stream) return *w;
   mgenx_log_ws* w = new mgenx_log_ws();
@@ -461,15 +458,12 @@ static mgenx_log_ws& ws_for(void* wsp, hipStream_t stream) {
   return *w;
 }
 
-extern "C" int mgenx_log_recv_run(void* wsp, bool binary, const uint8_t* slab,
-                                  uint64_t slab_bytes, const uint64_t* rec_off,
-                                  const uint32_t* rec_len,
-                                       uint64_t stride, const mgenx_cols* cols,
-                                       const mgenx_addr* src, const uint32_t* rx_sec,
-                                       const uint32_t* rx_usec, const int32_t* ttl, uint32_t n,
-                                       int protocol, uint32_t opts, char* text,
-                                       uint64_t text_cap, uint64_t* line_off,
-                                       hipStream_t stream, char* err, size_t errn) {
+int mgenx::log_recv_run(mgenx_log_ws* wsp, bool binary, const uint8_t* slab, uint64_t slab_bytes,
+                        const uint64_t* rec_off, const uint32_t* rec_len, uint64_t stride,
+                        const mgenx_cols* cols, const mgenx_addr* src, const uint32_t* rx_sec,
+                        const uint32_t* rx_usec, const int32_t* ttl, uint32_t n, int protocol,
+                        uint32_t opts, char* text, uint64_t text_cap, uint64_t* line_off,
+                        hipStream_t stream, char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   LogParams p;
   p.slab = slab; p.slab_bytes = slab_bytes; p.rec_off = rec_off; p.rec_len = rec_len;
@@ -482,25 +476,19 @@ extern "C" int mgenx_log_recv_run(void* wsp, bool binary, const uint8_t* slab,
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n + 1, stream);
-  const size_t len_bytes = (((size_t)n + 1) * 8 + 255) & ~(size_t)255;
+  const size_t len_bytes = a256(((size_t)n + 1) * 8);
   const size_t need = len_bytes + scan_bytes;
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "log: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  if (ws.mem.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "log: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  p.lens = static_cast<uint64_t*>(ws.mem);
+  p.lens = static_cast<uint64_t*>(ws.mem.p);
   // pass 1: lengths; line_off = exclusive scan of the n + 1 lengths (lens[n] = 0)
   if (binary) hipLaunchKernelGGL((log_kernel<false, true>), dim3(grid), dim3(kLogThreads), 0, stream, p);
   else hipLaunchKernelGGL((log_kernel<false, false>), dim3(grid), dim3(kLogThreads), 0, stream, p);
   hipLaunchKernelGGL(log_tail_kernel, dim3(1), dim3(64), 0, stream, p.lens, n);
   size_t have = scan_bytes;
-  if (hipcub::DeviceScan::ExclusiveSum(static_cast<uint8_t*>(ws.mem) + len_bytes, have, p.lens,
+  if (hipcub::DeviceScan::ExclusiveSum(static_cast<uint8_t*>(ws.mem.p) + len_bytes, have, p.lens,
                                        line_off, (int)n + 1, stream) != hipSuccess) {
     snprintf(err, errn, "log: scan failed");
     return MGENX_EDEVICE;
@@ -1306,40 +1294,33 @@ __global__ void __launch_bounds__(kLogThreads) binlog_line_kernel(BinParams p) {
 
 // per-stream scratch for the two-pass line formatters and the walk's scans
 static int rep_ws(mgenx_log_ws& ws, size_t need, void** out, char* err, size_t errn) {
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "report: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  if (ws.mem.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "report: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  *out = ws.mem;
+  *out = ws.mem.p;
   return MGENX_OK;
 }
 
-extern "C" int mgenx_report_build_run(const mgenx_flow_report* reps, uint32_t n_flows,
-                                      uint32_t per_flow, const uint32_t* count,
-                                      const mgenx_report_key* keys, uint8_t* sign,
-                                      const double* offset, const double* rq, uint8_t* items,
-                                      uint8_t* item_len, hipStream_t stream) {
+int mgenx::report_build_run(const mgenx_flow_report* reps, uint32_t n_flows, uint32_t per_flow,
+                            const uint32_t* count, const mgenx_report_key* keys, uint8_t* sign,
+                            const double* offset, const double* rq, uint8_t* items,
+                            uint8_t* item_len, hipStream_t stream) {
   if (!n_flows || !per_flow) return MGENX_OK;
   hipLaunchKernelGGL(mgenx::report_build_kernel, dim3((n_flows + 127) / 128), dim3(128), 0, stream,
                      reps, n_flows, per_flow, count, keys, sign, offset, rq, items, item_len);
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_report_lines_run(void* wsp, mgenx::RepLineParams* pp, hipStream_t stream,
-                                      char* err, size_t errn) {
+static int report_lines_run(mgenx_log_ws* wsp, mgenx::RepLineParams* pp, hipStream_t stream,
+                            char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   mgenx::RepLineParams& p = *pp;
   const uint32_t n = p.n;
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n + 1, stream);
-  const size_t len_bytes = (((size_t)n + 1) * 8 + 255) & ~(size_t)255;
+  const size_t len_bytes = a256(((size_t)n + 1) * 8);
   void* mem;
   int rc = rep_ws(ws, len_bytes + scan_bytes, &mem, err, errn);
   if (rc != MGENX_OK) return rc;
@@ -1359,15 +1340,15 @@ extern "C" int mgenx_report_lines_run(void* wsp, mgenx::RepLineParams* pp, hipSt
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_data_walk_run(void* wsp, mgenx::WalkParams* pp, uint32_t* totals,
-                                   hipStream_t stream, char* err, size_t errn) {
+static int data_walk_run(mgenx_log_ws* wsp, mgenx::WalkParams* pp, uint32_t* totals,
+                         hipStream_t stream, char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   mgenx::WalkParams& p = *pp;
   const uint32_t n = p.n;
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr,
                                          (uint32_t*)nullptr, (int)n + 1, stream);
-  const size_t b4 = (((size_t)n + 1) * 4 + 255) & ~(size_t)255;
+  const size_t b4 = a256(((size_t)n + 1) * 4);
   void* mem;
   int rc = rep_ws(ws, 4 * b4 + scan_bytes, &mem, err, errn);
   if (rc != MGENX_OK) return rc;
@@ -1397,10 +1378,9 @@ extern "C" int mgenx_data_walk_run(void* wsp, mgenx::WalkParams* pp, uint32_t* t
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_text_interleave_run(void* wsp, const mgenx_text_src* srcs, uint32_t n_src,
-                                         uint32_t n_rec, char* out, uint64_t cap,
-                                         uint64_t* rec_off, hipStream_t stream, char* err,
-                                         size_t errn) {
+int mgenx::text_interleave_run(mgenx_log_ws* wsp, const mgenx_text_src* srcs, uint32_t n_src,
+                               uint32_t n_rec, char* out, uint64_t cap, uint64_t* rec_off,
+                               hipStream_t stream, char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   mgenx::TextParams p;
   memset(&p, 0, sizeof(p));
@@ -1410,8 +1390,8 @@ extern "C" int mgenx_text_interleave_run(void* wsp, const mgenx_text_src* srcs, 
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n_rec + 1, stream);
-  const size_t len_bytes = (((size_t)n_rec + 1) * 8 + 255) & ~(size_t)255;
-  const size_t map_bytes = (((size_t)n_rec + 1) * 4 + 255) & ~(size_t)255;
+  const size_t len_bytes = a256(((size_t)n_rec + 1) * 8);
+  const size_t map_bytes = a256(((size_t)n_rec + 1) * 4);
   uint32_t n_scatter = 0;
   for (uint32_t s = 0; s < n_src; s++) n_scatter += srcs[s].kind == MGENX_TEXT_SCATTER;
   void* mem;
@@ -1461,10 +1441,10 @@ static mgenx::BinParams bin_params(const uint8_t* buf, const uint64_t* rec_off, 
   return p;
 }
 
-extern "C" int mgenx_binlog_parse_exec(const uint8_t* buf, const uint64_t* rec_off, uint32_t n,
-                                       uint64_t* msg_off, uint32_t* msg_len, mgenx_addr* src,
-                                       uint32_t* ev_sec, uint32_t* ev_usec, uint32_t* aux,
-                                       uint8_t* kind, uint8_t* proto, hipStream_t stream) {
+int mgenx::binlog_parse_exec(const uint8_t* buf, const uint64_t* rec_off, uint32_t n,
+                             uint64_t* msg_off, uint32_t* msg_len, mgenx_addr* src,
+                             uint32_t* ev_sec, uint32_t* ev_usec, uint32_t* aux, uint8_t* kind,
+                             uint8_t* proto, hipStream_t stream) {
   mgenx::BinParams p = bin_params(buf, rec_off, n, msg_off, msg_len, src, ev_sec, ev_usec, aux,
                                   kind, proto);
   if (p.n)
@@ -1473,14 +1453,12 @@ extern "C" int mgenx_binlog_parse_exec(const uint8_t* buf, const uint64_t* rec_o
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_binlog_lines_exec(void* wsp, const uint8_t* buf, const uint64_t* rec_off,
-                                       uint32_t n, uint64_t* msg_off, uint32_t* msg_len,
-                                       mgenx_addr* src, uint32_t* ev_sec, uint32_t* ev_usec,
-                                       uint32_t* aux, uint8_t* kind, uint8_t* proto,
-                                       const mgenx_cols* cols, uint32_t log_rx, uint32_t flush,
-                                       uint32_t opts, char* text, uint64_t cap,
-                                       uint64_t* line_off, hipStream_t stream, char* err,
-                                       size_t errn) {
+int mgenx::binlog_lines_exec(mgenx_log_ws* wsp, const uint8_t* buf, const uint64_t* rec_off,
+                             uint32_t n, uint64_t* msg_off, uint32_t* msg_len, mgenx_addr* src,
+                             uint32_t* ev_sec, uint32_t* ev_usec, uint32_t* aux, uint8_t* kind,
+                             uint8_t* proto, const mgenx_cols* cols, uint32_t log_rx,
+                             uint32_t flush, uint32_t opts, char* text, uint64_t cap,
+                             uint64_t* line_off, hipStream_t stream, char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   mgenx::BinParams p = bin_params(buf, rec_off, n, msg_off, msg_len, src, ev_sec, ev_usec, aux,
                                   kind, proto);
@@ -1490,7 +1468,7 @@ extern "C" int mgenx_binlog_lines_exec(void* wsp, const uint8_t* buf, const uint
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n + 1, stream);
-  const size_t len_bytes = (((size_t)n + 1) * 8 + 255) & ~(size_t)255;
+  const size_t len_bytes = a256(((size_t)n + 1) * 8);
   void* mem;
   int rc = rep_ws(ws, len_bytes + scan_bytes, &mem, err, errn);
   if (rc != MGENX_OK) return rc;
@@ -1512,31 +1490,30 @@ extern "C" int mgenx_binlog_lines_exec(void* wsp, const uint8_t* buf, const uint
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-extern "C" int mgenx_report_lines(void* ws, const uint8_t* items, const mgenx_flow_report* reps,
-                                  const uint32_t* count, uint32_t per_flow, const uint64_t* pairs,
-                                  const uint8_t* slab, const mgenx_addr* reporter,
-                                  const uint32_t* rx_sec, const uint32_t* rx_usec, uint32_t n,
-                                  uint32_t opts, const double* rq, char* text, uint64_t cap,
-                                  uint64_t* line_off, hipStream_t stream, char* err, size_t errn) {
+int mgenx::report_lines(mgenx_log_ws* ws, const uint8_t* items, const mgenx_flow_report* reps,
+                        const uint32_t* count, uint32_t per_flow, const uint64_t* pairs,
+                        const uint8_t* slab, const mgenx_addr* reporter, const uint32_t* rx_sec,
+                        const uint32_t* rx_usec, uint32_t n, uint32_t opts, const double* rq,
+                        char* text, uint64_t cap, uint64_t* line_off, hipStream_t stream, char* err,
+                        size_t errn) {
   mgenx::RepLineParams p;
   p.items = items; p.reps = reps; p.count = count; p.per_flow = per_flow; p.rep_pairs = pairs;
   p.slab = slab; p.reporter = reporter; p.rx_sec = rx_sec; p.rx_usec = rx_usec; p.n = n;
   p.opts = opts; p.rq = rq; p.text = reinterpret_cast<uint8_t*>(text); p.text_cap = cap;
   p.line_off = line_off; p.lens = nullptr;
-  return mgenx_report_lines_run(ws, &p, stream, err, errn);
+  return report_lines_run(ws, &p, stream, err, errn);
 }
 
-extern "C" int mgenx_data_walk_exec(void* ws, const uint8_t* slab, const uint64_t* rec_off,
-                                    uint64_t stride, const mgenx_cols* cols, uint32_t n,
-                                    uint32_t opts, const double* rq, uint8_t* status,
-                                    uint8_t* needs_host, uint32_t* cmds, uint32_t cmd_cap,
-                                    uint64_t* reps, uint32_t rep_cap, uint32_t* totals,
-                                    hipStream_t stream, char* err, size_t errn) {
+int mgenx::data_walk_exec(mgenx_log_ws* ws, const uint8_t* slab, const uint64_t* rec_off,
+                          uint64_t stride, const mgenx_cols* cols, uint32_t n, uint32_t opts,
+                          const double* rq, uint8_t* status, uint8_t* needs_host, uint32_t* cmds,
+                          uint32_t cmd_cap, uint64_t* reps, uint32_t rep_cap, uint32_t* totals,
+                          hipStream_t stream, char* err, size_t errn) {
   mgenx::WalkParams p;
   p.slab = slab; p.rec_off = rec_off; p.stride = stride; p.cols = *cols; p.n = n; p.opts = opts;
   p.rq = rq; p.status = status; p.needs_host = needs_host; p.cmds = cmds; p.cmd_cap = cmd_cap;
   p.reps = reps; p.rep_cap = rep_cap;
-  return mgenx_data_walk_run(ws, &p, totals, stream, err, errn);
+  return data_walk_run(ws, &p, totals, stream, err, errn);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1663,14 +1640,12 @@ __global__ void __launch_bounds__(kLogThreads) send_kernel(SendParams p) {
 
 }  // namespace mgenx
 
-extern "C" int mgenx_log_send_exec(void* wsp, const mgenx_flow_tmpl* tmpl,
-                                   const mgenx_pack_desc* desc, const uint16_t* src_port,
-                                   const uint32_t* out_len, const uint32_t* msg_total,
-                                   const uint8_t* slab, uint64_t slab_bytes,
-                                   const uint64_t* rec_off, uint64_t stride, uint32_t n,
-                                   int protocol, uint32_t opts, bool binary, uint8_t* out,
-                                   uint64_t out_cap, uint64_t* pos, hipStream_t stream,
-                                   char* err, size_t errn) {
+int mgenx::log_send_exec(mgenx_log_ws* wsp, const mgenx_flow_tmpl* tmpl,
+                         const mgenx_pack_desc* desc, const uint16_t* src_port,
+                         const uint32_t* out_len, const uint32_t* msg_total, const uint8_t* slab,
+                         uint64_t slab_bytes, const uint64_t* rec_off, uint64_t stride, uint32_t n,
+                         int protocol, uint32_t opts, bool binary, uint8_t* out, uint64_t out_cap,
+                         uint64_t* pos, hipStream_t stream, char* err, size_t errn) {
   mgenx_log_ws& ws = ws_for(wsp, stream);
   mgenx::SendParams p;
   p.tmpl = tmpl; p.desc = desc; p.src_port = src_port; p.out_len = out_len;
@@ -1680,7 +1655,7 @@ extern "C" int mgenx_log_send_exec(void* wsp, const mgenx_flow_tmpl* tmpl,
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n + 1, stream);
-  const size_t len_bytes = (((size_t)n + 1) * 8 + 255) & ~(size_t)255;
+  const size_t len_bytes = a256(((size_t)n + 1) * 8);
   void* mem;
   int rc = rep_ws(ws, len_bytes + scan_bytes, &mem, err, errn);
   if (rc != MGENX_OK) return rc;

@@ -14,7 +14,7 @@
 
 #include <stdio.h>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 #include "mgenx_logparse.hpp"
 
 namespace mgenx {
@@ -313,29 +313,27 @@ __global__ void __launch_bounds__(256) log_payload_kernel(ParseParams p) {
     dst[j] = (uint8_t)(lp::hex_val(src[2 * j]) << 4 | lp::hex_val(src[2 * j + 1]));
 }
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace mgenx
 
 using namespace mgenx;
 
-extern "C" size_t mgenx_text_index_ws(uint64_t nbytes) {
+size_t mgenx::text_index_ws(uint64_t nbytes) {
   const uint64_t n_tiles = (nbytes + kIdxTile - 1) / kIdxTile;
   size_t scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)n_tiles + 1, nullptr);
-  return up256((n_tiles + 1) * 8) + scan_bytes;
+  return a256((n_tiles + 1) * 8) + scan_bytes;
 }
 
-extern "C" int mgenx_text_index_run(void* ws, const uint8_t* text, uint64_t nbytes,
-                                    uint64_t* line_off, uint64_t cap, uint64_t* n_lines,
-                                    hipStream_t stream, char* err, size_t errn) {
+int mgenx::text_index_run(void* ws, const uint8_t* text, uint64_t nbytes, uint64_t* line_off,
+                          uint64_t cap, uint64_t* n_lines, hipStream_t stream, char* err,
+                          size_t errn) {
   if (nbytes == 0) {
     hipLaunchKernelGGL(text_index_empty_kernel, dim3(1), dim3(64), 0, stream, line_off, n_lines);
   } else {
     const uint32_t n_tiles = (uint32_t)((nbytes + kIdxTile - 1) / kIdxTile);
     uint64_t* counts = static_cast<uint64_t*>(ws);
-    const size_t cnt_bytes = up256(((size_t)n_tiles + 1) * 8);
+    const size_t cnt_bytes = a256(((size_t)n_tiles + 1) * 8);
     size_t scan_bytes = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t*)nullptr,
                                            (uint64_t*)nullptr, (int)n_tiles + 1, stream);
@@ -365,27 +363,27 @@ static void parse_scan_bytes(uint32_t n, size_t* day, size_t* pay) {
                                          (int)n + 1, nullptr);
 }
 
-extern "C" size_t mgenx_log_parse_ws(uint32_t n) {
+size_t mgenx::log_parse_ws(uint32_t n) {
   size_t day, pay;
   parse_scan_bytes(n, &day, &pay);
-  return up256((size_t)n * 16) + 2 * up256((size_t)n * 4) + up256(n) +
-         2 * up256(((size_t)n + 1) * 8) + up256(day > pay ? day : pay);
+  return a256((size_t)n * 16) + 2 * a256((size_t)n * 4) + a256(n) +
+         2 * a256(((size_t)n + 1) * 8) + a256(day > pay ? day : pay);
 }
 
-extern "C" int mgenx_log_parse_run(void* ws, const uint8_t* text, uint64_t nbytes,
-                                   const uint64_t* line_off, uint32_t n, uint32_t opts,
-                                   uint32_t day_base, const mgenx_logparse_out* out,
-                                   hipStream_t stream, char* err, size_t errn) {
+int mgenx::log_parse_run(void* ws, const uint8_t* text, uint64_t nbytes, const uint64_t* line_off,
+                         uint32_t n, uint32_t opts, uint32_t day_base,
+                         const mgenx_logparse_out* out, hipStream_t stream, char* err,
+                         size_t errn) {
   ParseParams p;
   p.text = text; p.nbytes = nbytes; p.line_off = line_off; p.n = n; p.opts = opts;
   p.day_base = day_base; p.out = *out;
   uint8_t* w = static_cast<uint8_t*>(ws);
-  p.elem = reinterpret_cast<DayElem*>(w); w += up256((size_t)n * 16);
-  p.rxs = reinterpret_cast<uint32_t*>(w); w += up256((size_t)n * 4);
-  p.rxu = reinterpret_cast<uint32_t*>(w); w += up256((size_t)n * 4);
-  p.kind = w; w += up256(n);
-  uint64_t* pay_len = reinterpret_cast<uint64_t*>(w); w += up256(((size_t)n + 1) * 8);
-  p.pay_pos = reinterpret_cast<uint64_t*>(w); w += up256(((size_t)n + 1) * 8);
+  p.elem = reinterpret_cast<DayElem*>(w); w += a256((size_t)n * 16);
+  p.rxs = reinterpret_cast<uint32_t*>(w); w += a256((size_t)n * 4);
+  p.rxu = reinterpret_cast<uint32_t*>(w); w += a256((size_t)n * 4);
+  p.kind = w; w += a256(n);
+  uint64_t* pay_len = reinterpret_cast<uint64_t*>(w); w += a256(((size_t)n + 1) * 8);
+  p.pay_pos = reinterpret_cast<uint64_t*>(w); w += a256(((size_t)n + 1) * 8);
   p.pay_len = out->payload_off ? pay_len : nullptr;
   size_t day_bytes, pay_bytes;
   parse_scan_bytes(n, &day_bytes, &pay_bytes);

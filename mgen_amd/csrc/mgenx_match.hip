@@ -16,7 +16,7 @@
 //   3. match_probe_kernel: a lane per recv record finds the owner or none, writes recv_send,
 //      counts into send_rx_count (atomicAdd) and send_first_rx (atomicMin); the orphans of a
 //      flow and the global counters are summed per wave before their atomics;
-//   4. the send records ordered by flow, stably (mgenx_flow_sort_run, as mgenx_flow_dist runs
+//   4. the send records ordered by flow, stably (mgenx::flow_sort_run, as mgenx_flow_dist runs
 //      it), and cut into chunks of kChunk sorted positions that ignore the flow edges.
 //      Every position is U (an undelivered owner), D (a delivered owner) or X (a send
 //      duplicate, which neither counts nor breaks a run).  A loss run is a segment of a
@@ -37,7 +37,7 @@
 #include <stdio.h>
 
 #include "mgenx_flowdist.hpp"
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -542,71 +542,42 @@ __global__ void match_side_kernel(const uint8_t* __restrict__ event,
 }  // namespace mgenx
 
 // ------------------------------------------------------------------------------------
-// host side (workspace owned by the context; see mgenx_api.hip)
+// host side (workspace owned by the context: struct mgenx_ctx, mgenx_internal.hpp)
 // ------------------------------------------------------------------------------------
 using namespace mgenx;
 
-extern "C" size_t mgenx_flow_sort_ws(uint32_t n, uint32_t n_flows);
-extern "C" int mgenx_flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n,
-                                   uint32_t n_flows, const uint32_t** keys, const uint32_t** order,
-                                   const uint32_t** bnd, hipStream_t stream, char* err,
-                                   size_t errn);
 
-struct mgenx_match_ws {
-  void* mem = nullptr;
-  size_t bytes = 0;
-};
-
-extern "C" void* mgenx_match_ws_new() { return new mgenx_match_ws(); }
-extern "C" void mgenx_match_ws_free(void* p) {
-  mgenx_match_ws* w = static_cast<mgenx_match_ws*>(p);
-  if (!w) return;
-  mgenx::dev_free(w->mem);
-  delete w;
-}
-
-extern "C" int mgenx_match_side_run(const uint8_t* event, const uint8_t* status,
-                                    const mgenx_addr* src, uint32_t n, uint32_t want_event,
-                                    mgenx_addr* src_out, uint8_t* err_out, hipStream_t stream) {
+int mgenx::match_side_run(const uint8_t* event, const uint8_t* status, const mgenx_addr* src,
+                          uint32_t n, uint32_t want_event, mgenx_addr* src_out, uint8_t* err_out,
+                          hipStream_t stream) {
   hipLaunchKernelGGL(match_side_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, event,
                      status, src, n, want_event, src_out, err_out);
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-static size_t mm_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ns <= 2^30 (the slot count fits 32 bits); nr, n_flows < 2^31
-extern "C" int mgenx_msg_match_run(void* wsp, const uint32_t* s_flow, const uint32_t* s_seq,
-                                   const uint32_t* s_sec, const uint32_t* s_usec,
-                                   const uint32_t* s_len, uint32_t ns, const uint32_t* r_flow,
-                                   const uint32_t* r_seq, const uint32_t* r_txs,
-                                   const uint32_t* r_txu, const uint32_t* r_rxs,
-                                   const uint32_t* r_rxu, uint32_t nr, uint32_t n_flows,
-                                   uint32_t opts, uint32_t* send_rx_count, uint32_t* send_first_rx,
-                                   uint32_t* recv_send, FlowMatch* flows, MatchStats* stats,
-                                   hipStream_t stream, char* err, size_t errn) {
-  mgenx_match_ws& ws = *static_cast<mgenx_match_ws*>(wsp);
+int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_seq,
+                         const uint32_t* s_sec, const uint32_t* s_usec, const uint32_t* s_len,
+                         uint32_t ns, const uint32_t* r_flow, const uint32_t* r_seq,
+                         const uint32_t* r_txs, const uint32_t* r_txu, const uint32_t* r_rxs,
+                         const uint32_t* r_rxu, uint32_t nr, uint32_t n_flows, uint32_t opts,
+                         uint32_t* send_rx_count, uint32_t* send_first_rx, uint32_t* recv_send,
+                         struct mgenx_flow_match* flows, struct mgenx_match_stats* stats,
+                         hipStream_t stream, char* err, size_t errn) {
   uint32_t n_slots = 64;  // a power of two >= 2 ns
   while (n_slots < 2u * ns) n_slots <<= 1;
   const bool account = ns > 0 && n_flows > 0;
   const uint32_t n_chunks = (ns + kChunk - 1u) / kChunk;
-  const size_t tab_b = mm_a256((size_t)n_slots * 4u), own_b = mm_a256((size_t)ns * 4u),
-               sort_b = account ? mm_a256(mgenx_flow_sort_ws(ns, n_flows)) : 0,
-               rec_b = mm_a256((size_t)ns * sizeof(MatchRec)), cls_b = mm_a256((size_t)ns),
-               c4 = mm_a256((size_t)n_chunks * 4u);
+  const size_t tab_b = a256((size_t)n_slots * 4u), own_b = a256((size_t)ns * 4u),
+               sort_b = account ? a256(mgenx::flow_sort_ws(ns, n_flows)) : 0,
+               rec_b = a256((size_t)ns * sizeof(MatchRec)), cls_b = a256((size_t)ns),
+               c4 = a256((size_t)n_chunks * 4u);
   const size_t need = tab_b + own_b + sort_b + rec_b + cls_b + 3 * c4;
-  if (ws.bytes < need) {
-    mgenx::dev_free(ws.mem);
-    ws.mem = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.mem, need) != hipSuccess) {
-      snprintf(err, errn, "msg_match: workspace of %zu bytes", need);
-      return MGENX_EDEVICE;
-    }
-    ws.bytes = need;
+  if (ws.reserve(need) != hipSuccess) {
+    snprintf(err, errn, "msg_match: workspace of %zu bytes", need);
+    return MGENX_EDEVICE;
   }
-  char* p = static_cast<char*>(ws.mem);
-  auto take = [&](size_t b) { char* q = p; p += b; return q; };
+  Carve take(ws.p);
   uint32_t* table = (uint32_t*)take(tab_b);
   uint32_t* own = (uint32_t*)take(own_b);
   void* sort_mem = take(sort_b);
@@ -639,7 +610,7 @@ extern "C" int mgenx_msg_match_run(void* wsp, const uint32_t* s_flow, const uint
   }
   if (!account) return MGENX_OK;
   const uint32_t *keys, *order, *bnd;
-  const int rc = mgenx_flow_sort_run(sort_mem, s_flow, ns, n_flows, &keys, &order, &bnd, stream,
+  const int rc = mgenx::flow_sort_run(sort_mem, s_flow, ns, n_flows, &keys, &order, &bnd, stream,
                                      err, errn);
   if (rc != MGENX_OK) return rc;
   const PackCols col = {own, send_rx_count, send_first_rx, s_len, s_sec, s_usec, r_rxs, r_rxu};

@@ -22,7 +22,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 #include "mgenx_pcapng.hpp"
 
 namespace mgenx {
@@ -316,12 +316,10 @@ static uint32_t host_u32(const uint8_t* b, bool sw) {
   return sw ? __builtin_bswap32(v) : v;
 }
 
-extern "C" {
-
 // the pcap_next loop (pcap2mgen.cpp:344) over a file image: global header (24 bytes), then
 // records of a 16-byte header {ts_sec, ts_frac, caplen, len} + caplen bytes
-int mgenx_pcap_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off, uint64_t cap,
-                     mgenx_pcap_info* info) {
+extern "C" int mgenx_pcap_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off,
+                                uint64_t cap, mgenx_pcap_info* info) {
   if (!buf || !info || (cap && !pkt_off)) return MGENX_EINVAL;
   memset(info, 0, sizeof(*info));
   if (nbytes < 24) return MGENX_EINVAL;
@@ -353,11 +351,11 @@ int mgenx_pcap_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off, uin
   return MGENX_OK;
 }
 
-int mgenx_pcap_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes, const uint64_t* dev_pkt_off,
-                         uint32_t n, uint32_t link_type, uint32_t flags, uint64_t* dev_udp_off,
-                         uint32_t* dev_udp_len, mgenx_addr* dev_src, int32_t* dev_ttl,
-                         uint32_t* dev_rx_sec, uint32_t* dev_rx_usec, uint8_t* dev_status,
-                         hipStream_t stream) {
+static int pcap_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                          uint32_t n, uint32_t link_type, uint32_t flags, uint64_t* dev_udp_off,
+                          uint32_t* dev_udp_len, mgenx_addr* dev_src, int32_t* dev_ttl,
+                          uint32_t* dev_rx_sec, uint32_t* dev_rx_usec, uint8_t* dev_status,
+                          hipStream_t stream) {
   PcapParams p;
   p.buf = dev_buf; p.buf_bytes = buf_bytes; p.pkt_off = dev_pkt_off; p.n = n;
   p.link_type = link_type; p.flags = flags; p.udp_off = dev_udp_off; p.udp_len = dev_udp_len;
@@ -367,13 +365,13 @@ int mgenx_pcap_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes, const uint6
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-int mgenx_pcapng_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes,
-                           const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if, uint32_t n,
-                           const mgenx_pcapng_if* dev_ifaces, uint32_t n_ifaces,
-                           uint32_t link_type, uint32_t flags, uint64_t* dev_udp_off,
-                           uint32_t* dev_udp_len, mgenx_addr* dev_src, int32_t* dev_ttl,
-                           uint32_t* dev_rx_sec, uint32_t* dev_rx_usec, uint8_t* dev_status,
-                           uint64_t* dev_data_off, uint32_t* dev_cap_len, hipStream_t stream) {
+static int pcapng_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes,
+                            const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if, uint32_t n,
+                            const mgenx_pcapng_if* dev_ifaces, uint32_t n_ifaces,
+                            uint32_t link_type, uint32_t flags, uint64_t* dev_udp_off,
+                            uint32_t* dev_udp_len, mgenx_addr* dev_src, int32_t* dev_ttl,
+                            uint32_t* dev_rx_sec, uint32_t* dev_rx_usec, uint8_t* dev_status,
+                            uint64_t* dev_data_off, uint32_t* dev_cap_len, hipStream_t stream) {
   PcapngParams g;
   PcapParams& p = g.c;
   p.buf = dev_buf; p.buf_bytes = buf_bytes; p.pkt_off = dev_pkt_off; p.n = n;
@@ -386,19 +384,19 @@ int mgenx_pcapng_parse_run(const uint8_t* dev_buf, uint64_t buf_bytes,
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-int mgenx_pcapng_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off, uint32_t* pkt_if,
-                       uint64_t cap, mgenx_pcapng_if* ifaces, uint32_t if_cap,
-                       mgenx_pcapng_info* info) {
+extern "C" int mgenx_pcapng_index(const uint8_t* buf, uint64_t nbytes, uint64_t* pkt_off,
+                                  uint32_t* pkt_if, uint64_t cap, mgenx_pcapng_if* ifaces,
+                                  uint32_t if_cap, mgenx_pcapng_info* info) {
   return mgenx::ng::index(buf, nbytes, pkt_off, pkt_if, cap, ifaces, if_cap, info);
 }
 
 // dev_cap_len null: classic records at dev_pkt_off; else pcapng, dev_pkt_off = the packets'
 // data offsets and dev_cap_len their captured lengths (mgenx_pcapng_parse's outputs)
-int mgenx_pcap_snap_run(uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
-                        const uint64_t* dev_pkt_off, const uint32_t* dev_cap_len, uint32_t n,
-                        uint32_t flags, uint8_t* dev_status, uint64_t* dev_udp_off,
-                        uint32_t* dev_udp_len, uint64_t* need, void* scan_tmp, size_t scan_bytes,
-                        hipStream_t stream) {
+static int pcap_snap_run(uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                         const uint64_t* dev_pkt_off, const uint32_t* dev_cap_len, uint32_t n,
+                         uint32_t flags, uint8_t* dev_status, uint64_t* dev_udp_off,
+                         uint32_t* dev_udp_len, uint64_t* need, void* scan_tmp, size_t scan_bytes,
+                         hipStream_t stream) {
   hipLaunchKernelGGL(pcap_snap_size_kernel, dim3((n + 256) / 256), dim3(256), 0, stream, dev_buf,
                      n, dev_status, dev_udp_off, need);
   size_t have = scan_bytes;
@@ -417,11 +415,88 @@ int mgenx_pcap_snap_run(uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_byte
   return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
 }
 
-size_t mgenx_pcap_snap_scan_bytes(uint32_t n) {
+static size_t pcap_snap_scan_bytes(uint32_t n) {
   size_t b = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr,
                                          (int)n + 1, (hipStream_t)0);
   return b;
+}
+
+// ---- the C ABI of the parse and snap steps ----
+using mgenx::set_err;
+
+extern "C" {
+
+int mgenx_pcap_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                     const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type,
+                     uint32_t flags, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                     mgenx_addr* dev_src, int32_t* dev_ttl, uint32_t* dev_rx_sec,
+                     uint32_t* dev_rx_usec, uint8_t* dev_status, void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_udp_off || !dev_udp_len || !dev_src || !dev_ttl ||
+      !dev_rx_sec || !dev_rx_usec || !dev_status)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return pcap_parse_run(dev_buf, buf_bytes, dev_pkt_off, n, link_type, flags, dev_udp_off,
+                              dev_udp_len, dev_src, dev_ttl, dev_rx_sec, dev_rx_usec, dev_status,
+                              (hipStream_t)stream);
+}
+
+// both snaps: dev_cap_len null = classic records at dev_pkt_off, else pcapng data offsets
+static int pcap_snap_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes,
+                         uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                         const uint32_t* dev_cap_len, uint32_t n, uint32_t flags,
+                         uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                         void* stream) {
+  if (!ctx || buf_bytes < file_bytes || n > 0x7FFFFFFEu) return MGENX_EINVAL;
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_status || !dev_udp_off || !dev_udp_len) return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  const size_t need_b = a256(((size_t)n + 1) * 8);
+  const size_t scan_b = pcap_snap_scan_bytes(n);
+  char* m = static_cast<char*>(ctx->snap.get(need_b + scan_b));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_snap workspace");
+  const int rc = pcap_snap_run(dev_buf, file_bytes, buf_bytes, dev_pkt_off, dev_cap_len, n,
+                                     flags, dev_status, dev_udp_off, dev_udp_len, (uint64_t*)m,
+                                     m + need_b, scan_b, (hipStream_t)stream);
+  return rc == MGENX_OK ? MGENX_OK : set_err(ctx, hipGetLastError(), "pcap_snap");
+}
+
+int mgenx_pcap_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                    const uint64_t* dev_pkt_off, uint32_t n, uint32_t flags, uint8_t* dev_status,
+                    uint64_t* dev_udp_off, uint32_t* dev_udp_len, void* stream) {
+  return pcap_snap_any(ctx, dev_buf, file_bytes, buf_bytes, dev_pkt_off, nullptr, n, flags,
+                       dev_status, dev_udp_off, dev_udp_len, stream);
+}
+
+int mgenx_pcapng_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                       const uint64_t* dev_pkt_off, const uint32_t* dev_pkt_if, uint32_t n,
+                       const mgenx_pcapng_if* dev_ifaces, uint32_t n_ifaces, uint32_t link_type,
+                       uint32_t flags, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                       mgenx_addr* dev_src, int32_t* dev_ttl, uint32_t* dev_rx_sec,
+                       uint32_t* dev_rx_usec, uint8_t* dev_status, uint64_t* dev_data_off,
+                       uint32_t* dev_cap_len, void* stream) {
+  if (!ctx) return MGENX_EINVAL;
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_pkt_if || (n_ifaces && !dev_ifaces) || !dev_udp_off ||
+      !dev_udp_len || !dev_src || !dev_ttl || !dev_rx_sec || !dev_rx_usec || !dev_status ||
+      !dev_data_off || !dev_cap_len)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  return pcapng_parse_run(dev_buf, buf_bytes, dev_pkt_off, dev_pkt_if, n, dev_ifaces,
+                                n_ifaces, link_type, flags, dev_udp_off, dev_udp_len, dev_src,
+                                dev_ttl, dev_rx_sec, dev_rx_usec, dev_status, dev_data_off,
+                                dev_cap_len, (hipStream_t)stream);
+}
+
+int mgenx_pcapng_snap(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t file_bytes, uint64_t buf_bytes,
+                      const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                      uint8_t* dev_status, uint64_t* dev_udp_off, uint32_t* dev_udp_len,
+                      void* stream) {
+  if (n && !dev_cap_len) return MGENX_EINVAL;
+  return pcap_snap_any(ctx, dev_buf, file_bytes, buf_bytes, dev_data_off, dev_cap_len, n, 0,
+                       dev_status, dev_udp_off, dev_udp_len, stream);
 }
 
 }  // extern "C"

@@ -37,11 +37,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include "mgenx_capture.hpp"
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
-extern "C" int mgenx_scan_run(void* ws, const uint8_t* s, uint64_t nbytes, int mode,
-                              uint64_t* rec_off, uint32_t* rec_len, uint64_t cap,
-                              mgenx_scan_info* info, hipStream_t stream, char* err, size_t errn);
 
 namespace mgenx {
 namespace ptcp {
@@ -458,8 +455,6 @@ __global__ void __launch_bounds__(256) tcp_copy_kernel(Params p) {
   }
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the most temporary storage any of the library calls below asks for
 static size_t cub_bytes(uint32_t n) {
   size_t best = 0, b = 0;
@@ -591,31 +586,30 @@ static size_t frame_cub_bytes(uint64_t cap, uint32_t n_streams) {
 }  // namespace mgenx
 
 using namespace mgenx::ptcp;
+using mgenx::a256;
+using mgenx::Carve;
 
-extern "C" size_t mgenx_pcap_tcp_ws(uint32_t n) {
+static size_t pcap_tcp_ws(uint32_t n) {
   const size_t N = n;
   return 4 * a256(N * 8) + a256(N * 40) + 4 * a256((N + 1) * 4) + 19 * a256(N * 4) +
          2 * a256(N) + 2 * a256((N + 1) * 8) + a256(kCntN * 8) + a256(cub_bytes(n));
 }
 
-// dev_data_off null: classic records at dev_pkt_off; else pcapng (as mgenx_defrag_run).  `mem`
-// holds mgenx_pcap_tcp_ws(n) bytes.  Synchronizes the stream once (the counters' read-back).
-extern "C" int mgenx_pcap_tcp_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off,
-                                  uint64_t buf_bytes, const uint64_t* dev_pkt_off,
-                                  const uint64_t* dev_data_off, const uint32_t* dev_cap_len,
-                                  uint32_t n, uint32_t link_type, uint32_t flags,
-                                  uint8_t* dev_status, mgenx_tcp_stream* dev_streams,
-                                  uint32_t stream_cap, uint64_t* dev_piece_end,
-                                  uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
-                                  hipStream_t stream, char* err, size_t errn) {
+// dev_data_off null: classic records at dev_pkt_off; else pcapng (as defrag_run of
+// mgenx_defrag.hip).  `mem` holds pcap_tcp_ws(n) bytes.  Synchronizes the stream once (the counters' read-back).
+static int pcap_tcp_run(void* mem, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                        const uint64_t* dev_pkt_off, const uint64_t* dev_data_off,
+                        const uint32_t* dev_cap_len, uint32_t n, uint32_t link_type, uint32_t flags,
+                        uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                        uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                        hipStream_t stream, char* err, size_t errn) {
   Params p;
   p.buf = dev_buf; p.limit = scratch_off; p.buf_bytes = buf_bytes; p.scratch_off = scratch_off;
   p.pkt_off = dev_pkt_off; p.data_off = dev_data_off; p.cap_len = dev_cap_len; p.n = n;
   p.link_type = link_type; p.flags = flags; p.status = dev_status; p.streams = dev_streams;
   p.piece_end = dev_piece_end; p.piece_pkt = dev_piece_pkt;
   const size_t N = n;
-  char* m = static_cast<char*>(mem);
-  auto take = [&](size_t b) { char* q = m; m += a256(b); return q; };
+  Carve take(mem);
   auto u32s = [&](size_t k) { return (uint32_t*)take(k * 4); };
   p.key_in = (uint64_t*)take(N * 8);
   p.key_out = (uint64_t*)take(N * 8);
@@ -725,34 +719,31 @@ extern "C" int mgenx_pcap_tcp_run(void* mem, uint8_t* dev_buf, uint64_t scratch_
   return e == hipSuccess ? MGENX_OK : fail(e, "pcap_tcp");
 }
 
-extern "C" size_t mgenx_tcp_frame_ws(uint32_t n_streams, uint64_t cap) {
+static size_t tcp_frame_ws(uint32_t n_streams, uint64_t cap) {
   const size_t S = n_streams, C = cap;
   return a256((S + 1) * 8) + 3 * a256(C * 8) + 4 * a256(C * 4) +
          a256(frame_cub_bytes(cap, n_streams));
 }
 
-// `mem` holds mgenx_tcp_frame_ws(n_streams, cap) bytes; scan_ws: the context's stream-scan
+// `mem` holds tcp_frame_ws(n_streams, cap) bytes; scan_ws: the context's stream-scan
 // workspace.  Synchronous: the stream table (checked against buf_bytes) and the short streams'
 // total are read back, and each long stream's scan synchronizes.
-extern "C" int mgenx_tcp_frame_run(void* mem, void* scan_ws, const uint8_t* dev_buf,
-                                   uint64_t buf_bytes, const mgenx_tcp_stream* dev_streams,
-                                   uint32_t n_streams,
-                                   const uint64_t* dev_piece_end, const uint32_t* dev_piece_pkt,
-                                   uint32_t n_pieces, const uint32_t* dev_pkt_rx_sec,
-                                   const uint32_t* dev_pkt_rx_usec, uint64_t long_bytes,
-                                   uint64_t* dev_rec_off, uint32_t* dev_rec_len,
-                                   uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt,
-                                   mgenx_addr* dev_rec_src, uint32_t* dev_rec_rx_sec,
-                                   uint32_t* dev_rec_rx_usec, uint64_t cap,
-                                   uint8_t* dev_stream_status, uint64_t* n_records,
-                                   hipStream_t stream, char* err, size_t errn) {
+static int tcp_frame_run(void* mem, mgenx_scan_ws* scan_ws, const uint8_t* dev_buf,
+                         uint64_t buf_bytes, const mgenx_tcp_stream* dev_streams,
+                         uint32_t n_streams, const uint64_t* dev_piece_end,
+                         const uint32_t* dev_piece_pkt, uint32_t n_pieces,
+                         const uint32_t* dev_pkt_rx_sec, const uint32_t* dev_pkt_rx_usec,
+                         uint64_t long_bytes, uint64_t* dev_rec_off, uint32_t* dev_rec_len,
+                         uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt, mgenx_addr* dev_rec_src,
+                         uint32_t* dev_rec_rx_sec, uint32_t* dev_rec_rx_usec, uint64_t cap,
+                         uint8_t* dev_stream_status, uint64_t* n_records, hipStream_t stream,
+                         char* err, size_t errn) {
   Frame f;
   f.buf = dev_buf; f.streams = dev_streams; f.n_streams = n_streams;
   f.piece_end = dev_piece_end; f.piece_pkt = dev_piece_pkt; f.n_pieces = n_pieces;
   f.long_bytes = long_bytes ? long_bytes : kDefaultLongBytes;
   f.cap = cap; f.stream_status = dev_stream_status;
-  char* m = static_cast<char*>(mem);
-  auto take = [&](size_t b) { char* q = m; m += a256(b); return q; };
+  Carve take(mem);
   f.count = (uint64_t*)take(((size_t)n_streams + 1) * 8);
   f.t_off = (uint64_t*)take(cap * 8);
   uint64_t* key_in = (uint64_t*)take(cap * 8);
@@ -794,7 +785,7 @@ extern "C" int mgenx_tcp_frame_run(void* mem, void* scan_ws, const uint8_t* dev_
     const uint64_t at = total < cap ? total : cap;  // where this stream's records go
     mgenx_scan_info info;
     memset(&info, 0, sizeof(info));
-    const int rc = mgenx_scan_run(scan_ws, dev_buf + hs[s].off, hs[s].len, MGENX_SCAN_TCP,
+    const int rc = mgenx::scan_run(scan_ws, dev_buf + hs[s].off, hs[s].len, MGENX_SCAN_TCP,
                                   f.t_off + at, f.t_len + at, cap - at, &info, stream, err, errn);
     if (rc != MGENX_OK) return rc;
     const uint64_t wrote = info.n_records < cap - at ? info.n_records : cap - at;
@@ -823,3 +814,82 @@ extern "C" int mgenx_tcp_frame_run(void* mem, void* scan_ws, const uint8_t* dev_
   if (e == hipSuccess) e = hipGetLastError();
   return e == hipSuccess ? MGENX_OK : fail(e, "tcp_frame");
 }
+
+// ---- the C ABI of the TCP reassembly and framing steps ----
+using mgenx::set_err;
+
+extern "C" {
+
+// both TCP reassemblies: dev_data_off null = classic records, else pcapng packet blocks
+static int pcap_tcp_any(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off,
+                        uint64_t buf_bytes, const uint64_t* dev_pkt_off,
+                        const uint64_t* dev_data_off, const uint32_t* dev_cap_len, uint32_t n,
+                        uint32_t link_type, uint32_t flags, uint8_t* dev_status,
+                        mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                        uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                        void* stream) {
+  if (!ctx || !stats || buf_bytes < scratch_off || n > 0x7FFFFFFEu) return MGENX_EINVAL;
+  memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MGENX_OK;
+  if (!dev_buf || !dev_pkt_off || !dev_status || (stream_cap && !dev_streams) ||
+      !dev_piece_end || !dev_piece_pkt)
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  void* m = ctx->ptcp.get(pcap_tcp_ws(n));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "pcap_tcp workspace");
+  return pcap_tcp_run(m, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                            dev_cap_len, n, link_type, flags, dev_status, dev_streams,
+                            stream_cap, dev_piece_end, dev_piece_pkt, stats,
+                            (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+int mgenx_pcap_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                   const uint64_t* dev_pkt_off, uint32_t n, uint32_t link_type, uint32_t flags,
+                   uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                   uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                   void* stream) {
+  return pcap_tcp_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, nullptr, nullptr, n,
+                      link_type, flags, dev_status, dev_streams, stream_cap, dev_piece_end,
+                      dev_piece_pkt, stats, stream);
+}
+
+int mgenx_pcapng_tcp(mgenx_ctx* ctx, uint8_t* dev_buf, uint64_t scratch_off, uint64_t buf_bytes,
+                     const uint64_t* dev_pkt_off, const uint64_t* dev_data_off,
+                     const uint32_t* dev_cap_len, uint32_t n, uint32_t link_type, uint32_t flags,
+                     uint8_t* dev_status, mgenx_tcp_stream* dev_streams, uint32_t stream_cap,
+                     uint64_t* dev_piece_end, uint32_t* dev_piece_pkt, mgenx_tcp_stats* stats,
+                     void* stream) {
+  if (n && (!dev_data_off || !dev_cap_len)) return MGENX_EINVAL;
+  return pcap_tcp_any(ctx, dev_buf, scratch_off, buf_bytes, dev_pkt_off, dev_data_off,
+                      dev_cap_len, n, link_type, flags, dev_status, dev_streams, stream_cap,
+                      dev_piece_end, dev_piece_pkt, stats, stream);
+}
+
+int mgenx_tcp_frame(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                    const mgenx_tcp_stream* dev_streams, uint32_t n_streams,
+                    const uint64_t* dev_piece_end, const uint32_t* dev_piece_pkt,
+                    uint32_t n_pieces, const uint32_t* dev_pkt_rx_sec,
+                    const uint32_t* dev_pkt_rx_usec, uint64_t long_bytes, uint64_t* dev_rec_off,
+                    uint32_t* dev_rec_len, uint32_t* dev_rec_stream, uint32_t* dev_rec_pkt,
+                    mgenx_addr* dev_rec_src, uint32_t* dev_rec_rx_sec, uint32_t* dev_rec_rx_usec,
+                    uint64_t cap, uint8_t* dev_stream_status, uint64_t* n_records, void* stream) {
+  if (!ctx || !n_records || n_streams > 0x7FFFFFFEu || cap > 0x7FFFFFFEu) return MGENX_EINVAL;
+  *n_records = 0;
+  if (n_streams == 0) return MGENX_OK;
+  if (!dev_buf || !dev_streams || !dev_stream_status || (n_pieces && (!dev_piece_end ||
+      !dev_piece_pkt)) || !dev_pkt_rx_sec || !dev_pkt_rx_usec ||
+      (cap && (!dev_rec_off || !dev_rec_len || !dev_rec_stream || !dev_rec_pkt || !dev_rec_src ||
+               !dev_rec_rx_sec || !dev_rec_rx_usec)))
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  if (!ctx->scan_ws) ctx->scan_ws = mgenx::scan_ws_new();
+  void* m = ctx->tcpf.get(tcp_frame_ws(n_streams, cap));
+  if (!m) return set_err(ctx, hipErrorOutOfMemory, "tcp_frame workspace");
+  return tcp_frame_run(m, ctx->scan_ws, dev_buf, buf_bytes, dev_streams, n_streams, dev_piece_end,
+                             dev_piece_pkt, n_pieces, dev_pkt_rx_sec, dev_pkt_rx_usec, long_bytes,
+                             dev_rec_off, dev_rec_len, dev_rec_stream, dev_rec_pkt, dev_rec_src,
+                             dev_rec_rx_sec, dev_rec_rx_usec, cap, dev_stream_status, n_records,
+                             (hipStream_t)stream, ctx->err, sizeof(ctx->err));
+}
+
+}  // extern "C"

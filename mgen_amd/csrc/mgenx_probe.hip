@@ -1,6 +1,6 @@
 // mgenx_probe.hip -- memory-pattern probes of the diagnostics build (mgenx_diag_stream_read*,
 // mgenx_diag_group_rw): no unpack code, and nothing at all in the product library.
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 #if MGENX_DIAG
 namespace mgenx {
@@ -172,8 +172,9 @@ hipError_t launch_group_rw(const uint8_t* p, uint64_t bytes, uint8_t* out, int m
                            hipStream_t stream) {
   const uint32_t ng = (uint32_t)(bytes / 16384);
   if (mode >= 4096) {  // 4096 + 16 * ring_sel + 4 * bar + pol
-    static uint32_t* counter = nullptr;
-    if (!counter && hipMalloc((void**)&counter, 256) != hipSuccess) return hipErrorOutOfMemory;
+    static DevBuf counter_buf;  // (kept for the life of the process)
+    uint32_t* counter = static_cast<uint32_t*>(counter_buf.get(256));
+    if (!counter) return hipErrorOutOfMemory;
     hipError_t e = hipMemsetAsync(counter, 0, 16, stream);
     if (e != hipSuccess) return e;
     const int m = mode - 4096;

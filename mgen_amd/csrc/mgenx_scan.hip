@@ -37,7 +37,7 @@
 
 #include <vector>
 
-#include "mgenx_kernels.hpp"
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -977,32 +977,11 @@ __global__ void scan_resolve_kernel(const uint8_t* __restrict__ s, uint64_t nbyt
 // ------------------------------------------------------------------------------------
 using namespace mgenx;
 
-namespace {
-
-struct ScanWork {
-  void* mem = nullptr;
-  size_t bytes = 0;
-};
-
-hipError_t ensure(ScanWork& w, size_t need) {
-  if (w.bytes >= need) return hipSuccess;
-  mgenx::dev_free(w.mem);
-  w.mem = nullptr;
-  w.bytes = 0;
-  hipError_t e = hipMalloc(&w.mem, need);
-  if (e == hipSuccess) w.bytes = need;
-  return e;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}  // namespace
-
 // The workspace lives with the context (grown on demand, freed by mgenx_ctx_destroy via
-// mgenx_scan_ws_free).  It also keeps the candidate tables of the last stream built, which
+// mgenx::scan_ws_free).  It also keeps the candidate tables of the last stream built, which
 // mgenx_stream_scan_range may reuse on request.
 struct mgenx_scan_ws {
-  ScanWork slots, cands, tabs, small;
+  DevBuf slots, cands, tabs, small;
   // host-mapped (fine-grained) words the kernels write their results to: [0] candidate
   // total, [2..3] chain end -- no copy operations on the common path
   uint64_t* host = nullptr;
@@ -1033,19 +1012,17 @@ struct mgenx_scan_ws {
   // sized spec_cap.  After a stream where it was not the chain the next prune_skip scans do not
   // try it (backoff 2, 4, ... 64 scans; reset on success)
   uint32_t prune_skip = 0, prune_backoff = 0;
-  ScanWork chain;        // the chain kernel's look-back words
+  DevBuf chain;          // the chain kernel's look-back words
   uint32_t chain_epoch = 0;
   ChainAux* chain_host = nullptr;      // [kChainGroups] group summaries (host-mapped)
   ChainAux* chain_host_dev = nullptr;
   std::vector<ChainAux> chain_seen;    // the summaries as read
 };
 
-extern "C" void* mgenx_scan_ws_new() { return new mgenx_scan_ws(); }
-extern "C" void mgenx_scan_ws_free(void* p) {
-  mgenx_scan_ws* w = static_cast<mgenx_scan_ws*>(p);
+mgenx_scan_ws* mgenx::scan_ws_new() { return new mgenx_scan_ws(); }
+void mgenx::scan_ws_free(mgenx_scan_ws* w) {
   if (!w) return;
-  for (ScanWork* x : {&w->slots, &w->cands, &w->tabs, &w->small, &w->chain})
-    mgenx::dev_free(x->mem);
+  for (DevBuf* x : {&w->slots, &w->cands, &w->tabs, &w->small, &w->chain}) x->release();
   mgenx::host_free(w->host);
   mgenx::host_free(w->chain_host);
   delete w;
@@ -1078,7 +1055,7 @@ size_t tab_bytes(uint32_t stride, int levels) {
 // the small device area and the host-mapped result words
 int ensure_small(mgenx_scan_ws& ws, const Fail& fail) {
   hipError_t e;
-  if ((e = ensure(ws.small, 4096)) != hipSuccess) return fail(e, "scan workspace");
+  if ((e = ws.small.reserve(4096)) != hipSuccess) return fail(e, "scan workspace");
   if (!ws.host) {
     void* hp = nullptr;
     if ((e = hipHostMalloc(&hp, 64, hipHostMallocMapped)) != hipSuccess)
@@ -1097,8 +1074,8 @@ uint32_t link_grid(uint32_t nb) { return (nb + 4 * kLinkPerWave - 1) / (4 * kLin
 void lay_tables(mgenx_scan_ws& ws, uint32_t stride, int levels) {
   ws.stride = stride;
   ws.levels = levels;
-  ws.cand = static_cast<uint64_t*>(ws.cands.mem);
-  ws.ups = static_cast<uint32_t*>(ws.tabs.mem);
+  ws.cand = static_cast<uint64_t*>(ws.cands.p);
+  ws.ups = static_cast<uint32_t*>(ws.tabs.p);
   ws.dists = ws.ups + (size_t)(levels + 1) * stride;
   ws.ups2 = ws.dists + (size_t)(levels + 1) * stride;
   ws.ups3 = ws.ups2 + (size_t)levels * stride;
@@ -1147,18 +1124,18 @@ int scan_build(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, int mode, h
     return MGENX_OK;
   }
   const uint32_t nb = (uint32_t)n_blocks64;
-  const size_t slot_b = align256((size_t)nb * kScanSlots * 4);
-  const size_t cnt_b = align256((size_t)(nb + 1) * 8);
+  const size_t slot_b = a256((size_t)nb * kScanSlots * 4);
+  const size_t cnt_b = a256((size_t)(nb + 1) * 8);
   size_t cub_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, (const uint64_t*)nullptr,
                                          (uint64_t*)nullptr, (int)(nb + 1), stream);
-  if ((e = ensure(ws.slots, slot_b + 2 * cnt_b + align256(cub_bytes))) != hipSuccess)
+  if ((e = ws.slots.reserve(slot_b + 2 * cnt_b + a256(cub_bytes))) != hipSuccess)
     return fail(e, "scan workspace");
-  uint32_t* d_slots = static_cast<uint32_t*>(ws.slots.mem);
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(static_cast<char*>(ws.slots.mem) + slot_b);
+  uint32_t* d_slots = static_cast<uint32_t*>(ws.slots.p);
+  uint64_t* d_counts = reinterpret_cast<uint64_t*>(static_cast<char*>(ws.slots.p) + slot_b);
   uint64_t* d_base = d_counts + cnt_b / 8;
-  void* d_cub = static_cast<char*>(ws.slots.mem) + slot_b + 2 * cnt_b;
-  uint32_t* irregular = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.small.mem) + 2048);
+  void* d_cub = static_cast<char*>(ws.slots.p) + slot_b + 2 * cnt_b;
+  uint32_t* irregular = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.small.p) + 2048);
   auto detect = scan_detect_kernel<false>;
 #if MGENX_DIAG
   if (const char* v = getenv("MGENX_SCAN_PLAIN"))
@@ -1186,8 +1163,8 @@ int scan_build(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, int mode, h
     // in scan_walk, not correctness)
     const uint64_t want = ws.last_records ? ws.last_records : cap;  // 4^levels + 1 records
     const int levels = levels_for(std::min<uint64_t>(want, cap));
-    if ((e = ensure(ws.cands, (size_t)cap * 8)) != hipSuccess ||
-        (e = ensure(ws.tabs, tab_bytes(cap, levels))) != hipSuccess)
+    if ((e = ws.cands.reserve((size_t)cap * 8)) != hipSuccess ||
+        (e = ws.tabs.reserve(tab_bytes(cap, levels))) != hipSuccess)
       return fail(e, "scan workspace");
     ws.key_s = s;
     ws.key_n = nbytes;
@@ -1199,7 +1176,7 @@ int scan_build(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, int mode, h
                        d_slots, d_counts, d_base, nb, ws.cand, ws.ups, ws.dists, (uint64_t)cap,
                        irregular);
     // (the lifting levels follow only when the chain is not the candidate list itself:
-    // mgenx_scan_run, after its one sync)
+    // mgenx::scan_run, after its one sync)
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "scan launch");
     return MGENX_OK;
   }
@@ -1219,8 +1196,8 @@ int scan_build(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, int mode, h
   const int levels = levels_for(n);
   // the next whole-stream scan speculates on about this many candidates
   ws.spec_cap = (uint32_t)std::min<uint64_t>((uint64_t)n + n / 8 + 1024, 0xFFFFFFF0u);
-  if ((e = ensure(ws.cands, (size_t)n * 8)) != hipSuccess) return fail(e, "scan workspace");
-  if ((e = ensure(ws.tabs, tab_bytes(n, levels))) != hipSuccess)
+  if ((e = ws.cands.reserve((size_t)n * 8)) != hipSuccess) return fail(e, "scan workspace");
+  if ((e = ws.tabs.reserve(tab_bytes(n, levels))) != hipSuccess)
     return fail(e, "scan workspace");
   ws.n = n;
   lay_tables(ws, n, levels);
@@ -1249,7 +1226,7 @@ int scan_walk(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, int mode, ui
   hipError_t e;
   mgenx_scan_info out;
   memset(&out, 0, sizeof(out));
-  ResolveState* d_st = reinterpret_cast<ResolveState*>(ws.small.mem);
+  ResolveState* d_st = reinterpret_cast<ResolveState*>(ws.small.p);
   ChainEnd* d_end = reinterpret_cast<ChainEnd*>(ws.host_dev + 2);
   const volatile uint64_t* h_end = ws.host + 2;
   uint64_t pos = entry, total = 0;
@@ -1361,25 +1338,25 @@ int scan_chain(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, uint64_t* r
     ws.chain_host_dev = static_cast<ChainAux*>(dp);
   }
   const uint32_t nb = (uint32_t)((nbytes + kScanBlockBytes - 1) / kScanBlockBytes);
-  const size_t slot_b = align256((size_t)nb * kScanSlots * 4);
-  const size_t cnt_b = align256((size_t)(nb + 1) * 8);
-  if ((e = ensure(ws.slots, slot_b + 2 * cnt_b)) != hipSuccess) return fail(e, "scan workspace");
-  uint32_t* d_slots = static_cast<uint32_t*>(ws.slots.mem);
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(static_cast<char*>(ws.slots.mem) + slot_b);
+  const size_t slot_b = a256((size_t)nb * kScanSlots * 4);
+  const size_t cnt_b = a256((size_t)(nb + 1) * 8);
+  if ((e = ws.slots.reserve(slot_b + 2 * cnt_b)) != hipSuccess) return fail(e, "scan workspace");
+  uint32_t* d_slots = static_cast<uint32_t*>(ws.slots.p);
+  uint64_t* d_counts = reinterpret_cast<uint64_t*>(static_cast<char*>(ws.slots.p) + slot_b);
   uint32_t groups = std::max<uint32_t>((nb + kChainBlocks - 1) / kChainBlocks,
                                        (ws.spec_cap + 2047) / 2048);
   groups = std::min(std::max(groups, 1u), kChainGroups);
   const uint32_t per_group = (nb + groups - 1) / groups;
   groups = (nb + per_group - 1) / per_group;
   // the look-back words (epoch-tagged: cleared only when the 22-bit epoch wraps)
-  if (!ws.chain.mem) {
-    if ((e = ensure(ws.chain, (size_t)kChainGroups * 8)) != hipSuccess ||
-        (e = hipMemsetAsync(ws.chain.mem, 0, ws.chain.bytes, stream)) != hipSuccess)
+  if (!ws.chain.p) {
+    if ((e = ws.chain.reserve((size_t)kChainGroups * 8)) != hipSuccess ||
+        (e = hipMemsetAsync(ws.chain.p, 0, ws.chain.bytes, stream)) != hipSuccess)
       return fail(e, "scan workspace");
     ws.chain_epoch = 0;
   }
   if (++ws.chain_epoch >= kChainEpochs) {
-    if ((e = hipMemsetAsync(ws.chain.mem, 0, ws.chain.bytes, stream)) != hipSuccess)
+    if ((e = hipMemsetAsync(ws.chain.p, 0, ws.chain.bytes, stream)) != hipSuccess)
       return fail(e, "scan workspace");
     memset(ws.chain_host, 0, kChainGroups * sizeof(ChainAux));  // (no kernel of ours runs now)
     ws.chain_epoch = 1;
@@ -1390,7 +1367,7 @@ int scan_chain(mgenx_scan_ws& ws, const uint8_t* s, uint64_t nbytes, uint64_t* r
                      (uint32_t*)nullptr);
   hipLaunchKernelGGL(scan_chain_kernel, dim3(groups), dim3(kChainThreads), 0, stream,
                      (const uint32_t*)d_slots, (const uint64_t*)d_counts, nbytes, nb, per_group,
-                     ws.chain_epoch, static_cast<uint64_t*>(ws.chain.mem), cap, rec_off, rec_len,
+                     ws.chain_epoch, static_cast<uint64_t*>(ws.chain.p), cap, rec_off, rec_len,
                      ws.chain_host_dev);
   if ((e = hipGetLastError()) != hipSuccess) return fail(e, "scan launch");
   // done when every group's summary carries this scan's epoch (each group writes it after its
@@ -1473,10 +1450,10 @@ extern "C" int mgenx_diag_chain_prof(unsigned long long* out) {
 #endif
 
 // Whole-stream scan from offset 0 (synchronous on `stream`).
-extern "C" int mgenx_scan_run(void* wsp, const uint8_t* s, uint64_t nbytes, int mode,
-                              uint64_t* rec_off, uint32_t* rec_len, uint64_t cap,
-                              mgenx_scan_info* info, hipStream_t stream, char* err, size_t errn) {
-  mgenx_scan_ws& ws = *static_cast<mgenx_scan_ws*>(wsp);
+int mgenx::scan_run(mgenx_scan_ws* wsp, const uint8_t* s, uint64_t nbytes, int mode,
+                    uint64_t* rec_off, uint32_t* rec_len, uint64_t cap, mgenx_scan_info* info,
+                    hipStream_t stream, char* err, size_t errn) {
+  mgenx_scan_ws& ws = *wsp;
   const Fail fail{err, errn};
   const bool try_chain = ws.prune_skip == 0;
   if (ws.prune_skip) ws.prune_skip--;
@@ -1504,8 +1481,8 @@ extern "C" int mgenx_scan_run(void* wsp, const uint8_t* s, uint64_t nbytes, int 
     ChainEnd* d_end = reinterpret_cast<ChainEnd*>(ws.host_dev + 2);
     const volatile uint64_t* h_end = ws.host + 2;
     const uint32_t* irregular =
-        reinterpret_cast<const uint32_t*>(static_cast<char*>(ws.small.mem) + 2048);
-    uint32_t* regular = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.small.mem) + 2052);
+        reinterpret_cast<const uint32_t*>(static_cast<char*>(ws.small.p) + 2048);
+    uint32_t* regular = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.small.p) + 2052);
     hipLaunchKernelGGL(scan_enum_regular_kernel, dim3((scap + 255) / 256), dim3(256), 0, stream,
                        s, ws.cand, ws.spec_total, irregular, scap, cap, rec_off, rec_len, d_end,
                        regular, ws.host_dev + 5);
@@ -1556,11 +1533,11 @@ extern "C" int mgenx_scan_run(void* wsp, const uint8_t* s, uint64_t nbytes, int 
 
 // One shard of a stream split over ranks: builds the tables and reports, for each candidate
 // below `window`, where its chain leaves [.., limit).
-extern "C" int mgenx_scan_exits_run(void* wsp, const uint8_t* s, uint64_t nbytes, int mode,
-                                    uint64_t window, uint64_t limit, uint64_t* entries,
-                                    uint64_t* exits, uint32_t cap, uint32_t* candidates,
-                                    hipStream_t stream, char* err, size_t errn) {
-  mgenx_scan_ws& ws = *static_cast<mgenx_scan_ws*>(wsp);
+int mgenx::scan_exits_run(mgenx_scan_ws* wsp, const uint8_t* s, uint64_t nbytes, int mode,
+                          uint64_t window, uint64_t limit, uint64_t* entries, uint64_t* exits,
+                          uint32_t cap, uint32_t* candidates, hipStream_t stream, char* err,
+                          size_t errn) {
+  mgenx_scan_ws& ws = *wsp;
   const Fail fail{err, errn};
   int rc = scan_build(ws, s, nbytes, mode, stream, fail);
   if (rc != MGENX_OK) return rc;
@@ -1576,11 +1553,11 @@ extern "C" int mgenx_scan_exits_run(void* wsp, const uint8_t* s, uint64_t nbytes
 // The records of [entry, limit) (synchronous).  reuse: the tables of the previous build on
 // this workspace are for this same stream (pointer, size, mode; the caller vouches that the
 // bytes are unchanged).
-extern "C" int mgenx_scan_range_run(void* wsp, const uint8_t* s, uint64_t nbytes, int mode,
-                                    uint64_t entry, uint64_t limit, int reuse, uint64_t* rec_off,
-                                    uint32_t* rec_len, uint64_t cap, mgenx_scan_info* info,
-                                    hipStream_t stream, char* err, size_t errn) {
-  mgenx_scan_ws& ws = *static_cast<mgenx_scan_ws*>(wsp);
+int mgenx::scan_range_run(mgenx_scan_ws* wsp, const uint8_t* s, uint64_t nbytes, int mode,
+                          uint64_t entry, uint64_t limit, int reuse, uint64_t* rec_off,
+                          uint32_t* rec_len, uint64_t cap, mgenx_scan_info* info,
+                          hipStream_t stream, char* err, size_t errn) {
+  mgenx_scan_ws& ws = *wsp;
   const Fail fail{err, errn};
   if (reuse) {
     if (ws.key_s != s || ws.key_n != nbytes || ws.key_mode != mode) {

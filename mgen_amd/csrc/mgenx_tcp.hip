@@ -25,7 +25,18 @@
 //                     ComputeCRC32 does) -- and writes the big-endian trailer.
 #include <hip/hip_runtime.h>
 
-#include "mgenx_kernels.hpp"
+#include <stdio.h>
+#include <string.h>
+
+#include <atomic>
+#include <chrono>
+#include <emmintrin.h>
+#include <immintrin.h>
+#include <utility>
+
+#include <hipcub/hipcub.hpp>
+
+#include "mgenx_internal.hpp"
 
 namespace mgenx {
 
@@ -360,3 +371,181 @@ hipError_t launch_tcp_plan0(const mgenx_flow_tmpl* tmpl, const mgenx_pack_desc* 
 }
 
 }  // namespace mgenx
+
+// ---- the transmit plan on the host (mgenx_pack_tcp) ----
+using mgenx::set_err;
+
+// the stream length and the round count (the plan kernel's maximum fragment count) for
+// the host, in one 16-byte copy (the exact path)
+__global__ void tcp_totals_kernel(const uint32_t* max_frag, uint32_t n, const uint64_t* off,
+                                  const uint64_t* bytes, uint64_t* out) {
+  out[0] = off[n - 1] + bytes[n - 1];  // (the exclusive scan's last offset + its message)
+  out[1] = *max_frag;
+}
+
+extern "C" {
+
+int mgenx_pack_tcp(mgenx_ctx* ctx, const mgenx_flow_tmpl* dev_tmpl, const uint32_t* dev_tmpl_crc,
+                   const mgenx_pack_desc* dev_desc, const uint32_t* dev_msg_total, uint32_t n,
+                   const uint8_t* dev_pool, uint8_t* dev_stream, uint64_t stream_cap,
+                   uint64_t* dev_msg_off, uint64_t* total_bytes, uint32_t opts,
+                   uint32_t fill_time, void* stream) {
+  if (!ctx || !total_bytes || (opts & ~(uint32_t)(MGENX_PACK_CHECKSUM | MGENX_PACK_RANDOM_FILL)))
+    return MGENX_EINVAL;
+  *total_bytes = 0;
+  if (n == 0) return MGENX_OK;
+  if (!dev_tmpl || !dev_tmpl_crc || !dev_desc || !dev_msg_total || !dev_msg_off)
+    return MGENX_EINVAL;
+  if ((opts & MGENX_PACK_RANDOM_FILL) && (!ctx->rand_ready || ctx->rand_time != fill_time))
+    return MGENX_EINVAL;
+  hipSetDevice(ctx->device);
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if (!ctx->tcp_host) {
+    void* hp = nullptr;
+    void* dp = nullptr;
+    if ((e = hipHostMalloc(&hp, 64, hipHostMallocMapped)) != hipSuccess) return set_err(ctx, e, "tcp");
+    memset(hp, 0, 64);
+    ctx->tcp_host = static_cast<uint64_t*>(hp);
+    if ((e = hipHostGetDevicePointer(&dp, hp, 0)) != hipSuccess) return set_err(ctx, e, "tcp");
+    ctx->tcp_host_dev = static_cast<uint64_t*>(dp);
+  }
+  // workspace: bytes[n], nfrag[n], cub (a scan of n items); per round: fd, foff, fbuf, ff,
+  // plen, crc, state x2; the maximum fragment count (exact path)
+  size_t cub_bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, (const uint64_t*)nullptr,
+                                         (uint64_t*)nullptr, (int)n, s);
+  const size_t b8 = mgenx::a256((size_t)n * 8), b4 = mgenx::a256((size_t)n * 4);
+  const size_t need = b8 + b4 + mgenx::a256(cub_bytes) +
+                      mgenx::a256((size_t)n * sizeof(mgenx_pack_desc)) +
+                      b8 + 4 * b4 + 2 * b4 + 256;
+  if ((e = ctx->tcp_ws.reserve(need)) != hipSuccess) return set_err(ctx, e, "tcp workspace");
+  mgenx::Carve take(ctx->tcp_ws.p);
+  uint64_t* bytes = (uint64_t*)take(b8);
+  uint32_t* nfrag = (uint32_t*)take(b4);
+  void* cub = take(cub_bytes);
+  mgenx_pack_desc* fd = (mgenx_pack_desc*)take((size_t)n * sizeof(mgenx_pack_desc));
+  uint64_t* foff = (uint64_t*)take(b8);
+  uint32_t* fbuf = (uint32_t*)take(b4);
+  uint32_t* ff = (uint32_t*)take(b4);
+  uint32_t* plen = (uint32_t*)take(b4);
+  uint32_t* crc = (uint32_t*)take(b4);
+  uint32_t* st[2] = {(uint32_t*)take(b4), (uint32_t*)take(b4)};
+  uint32_t* max_frag = (uint32_t*)take(256);
+  // the plan's words, in their own allocation (epoch-tagged: they must keep their place
+  // whatever n the next call brings): the skip word, then a look-back word and a maximum word
+  // a block
+  const uint32_t blocks = (n + mgenx::kTcpPlanMsgs - 1) / mgenx::kTcpPlanMsgs;
+  if (ctx->tcp_plan_blocks < blocks) {
+    mgenx::dev_free(ctx->tcp_plan);
+    ctx->tcp_plan = nullptr;
+    ctx->tcp_plan_blocks = 0;
+    const size_t pb = 256 + (size_t)blocks * 16;
+    if ((e = hipMalloc(&ctx->tcp_plan, pb)) != hipSuccess ||
+        (e = hipMemsetAsync(ctx->tcp_plan, 0, pb, s)) != hipSuccess)
+      return set_err(ctx, e, "tcp workspace");
+    ctx->tcp_plan_blocks = blocks;
+  }
+  if (++ctx->tcp_epoch >= mgenx::kTcpPlanEpochs) {  // wrap: clear the words (nothing in flight)
+    if ((e = hipStreamSynchronize(s)) != hipSuccess ||
+        (e = hipMemsetAsync(ctx->tcp_plan, 0, 256 + (size_t)ctx->tcp_plan_blocks * 16, s)) !=
+            hipSuccess)
+      return set_err(ctx, e, "tcp plan");
+    memset(ctx->tcp_host, 0, 64);
+    ctx->tcp_epoch = 1;
+  }
+  const uint32_t epoch = ctx->tcp_epoch;
+  uint32_t* skip = static_cast<uint32_t*>(ctx->tcp_plan);
+  uint64_t* status = reinterpret_cast<uint64_t*>(static_cast<char*>(ctx->tcp_plan) + 256);
+  uint64_t* fmax = status + ctx->tcp_plan_blocks;
+  const int ck = (opts & MGENX_PACK_CHECKSUM) ? 1 : 0;
+  // round r: fragment descriptors (round 0's come with the plan), then Pack -- which also
+  // stores the later buffers' copies, runs the CRC on through them and writes the trailer
+  auto round = [&](uint32_t r, const uint32_t* gate) -> int {
+    if (r > 0 && (e = mgenx::launch_tcp_frag(dev_desc, dev_msg_total, nfrag, dev_msg_off, n, r,
+                                             ck, st[(r + 1) & 1], fd, foff, fbuf, ff, s)) !=
+                     hipSuccess)
+      return set_err(ctx, e, "tcp fragments");
+    // (round 0's fragments start at the message offsets)
+    return mgenx::pack_common(ctx, dev_tmpl, dev_tmpl_crc, fd, n, dev_pool, dev_stream,
+                              stream_cap, r == 0 ? dev_msg_off : foff, 0, fbuf, nullptr, plen, crc,
+                              st[r & 1], opts | MGENX_PACK_RAW, fill_time, stream, ff, ck, gate);
+  };
+  // One launch plans every message, scans the offsets straight into the caller's array and
+  // writes round 0's descriptors; round 0 is queued behind it before the host has read the
+  // plan (gated on the device: when the stream exceeds stream_cap, or the plan failed, it
+  // stores nothing), so the GPU never waits for the host between back-to-back calls.  The
+  // host then spins on the plan's 16-byte verdict in host memory (not the stream's
+  // completion: round 0 keeps running), and queues any further rounds.
+  if ((e = mgenx::launch_tcp_plan0(dev_tmpl, dev_desc, dev_msg_total, n, ck, stream_cap, epoch,
+                                   status, fmax, dev_msg_off, nfrag, fd, fbuf, ff, skip,
+                                   ctx->tcp_host_dev, s)) != hipSuccess)
+    return set_err(ctx, e, "tcp plan");
+  const bool spec = dev_stream != nullptr;
+  if (spec) {
+    const int rc = round(0, skip);
+    if (rc != MGENX_OK) return rc;
+  }
+  auto verdict = [&]() {
+    const __m128i x = _mm_load_si128(reinterpret_cast<const __m128i*>(ctx->tcp_host));
+    return std::make_pair((uint64_t)_mm_cvtsi128_si64(x), (uint64_t)_mm_extract_epi64(x, 1));
+  };
+  std::pair<uint64_t, uint64_t> v;
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint64_t spins = 0;; spins++) {
+      std::atomic_signal_fence(std::memory_order_seq_cst);  // (a fresh load every poll)
+      v = verdict();
+      if ((uint32_t)(v.second >> 48) == epoch) break;
+      _mm_pause();
+      if ((spins & 0xFFFF) == 0xFFFF &&
+          std::chrono::steady_clock::now() - t0 > std::chrono::seconds(1)) {
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return set_err(ctx, e, "tcp plan");
+        v = verdict();
+        if ((uint32_t)(v.second >> 48) != epoch) {
+          snprintf(ctx->err, sizeof(ctx->err), "tcp plan: no verdict");
+          return MGENX_EDEVICE;
+        }
+        break;
+      }
+    }
+  }
+  uint64_t total = v.first;
+  uint32_t rounds = (uint32_t)(v.second & 0x7FFFFFFFu);
+  uint32_t r0 = spec ? 1u : 0u;  // the first round still to queue
+  if ((v.second >> 32) & 1u) {
+    // the exact path (the plan could not vouch for its offsets; round 0 stored nothing): the
+    // plan per message, the offsets by a device-wide scan, the totals read back
+    if ((e = hipMemsetAsync(max_frag, 0, 4, s)) != hipSuccess ||
+        (e = mgenx::launch_tcp_plan(dev_tmpl, dev_desc, dev_msg_total, n, bytes, nfrag, max_frag,
+                                    s)) != hipSuccess ||
+        (e = hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, (const uint64_t*)bytes, dev_msg_off,
+                                              (int)n, s)) != hipSuccess)
+      return set_err(ctx, e, "tcp plan");
+    hipLaunchKernelGGL(tcp_totals_kernel, dim3(1), dim3(1), 0, s, max_frag, n, dev_msg_off, bytes,
+                       ctx->tcp_host_dev);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return set_err(ctx, e, "tcp plan");
+    total = ((volatile uint64_t*)ctx->tcp_host)[0];
+    rounds = (uint32_t)((volatile uint64_t*)ctx->tcp_host)[1];
+    ((volatile uint64_t*)ctx->tcp_host)[1] = 0;  // (no stale epoch for the next call)
+    r0 = 0;
+  }
+  *total_bytes = total;
+  if (total > stream_cap || (total && !dev_stream)) {
+    snprintf(ctx->err, sizeof(ctx->err), "tcp: the stream needs %llu bytes",
+             (unsigned long long)total);
+    return MGENX_EINVAL;
+  }
+  for (uint32_t r = r0; r < rounds; r++) {
+    if (r == 0) {  // (exact path: round 0's descriptors from the fragment kernel)
+      if ((e = mgenx::launch_tcp_frag(dev_desc, dev_msg_total, nfrag, dev_msg_off, n, 0, ck,
+                                      st[1], fd, foff, fbuf, ff, s)) != hipSuccess)
+        return set_err(ctx, e, "tcp fragments");
+    }
+    const int rc = round(r, nullptr);
+    if (rc != MGENX_OK) return rc;
+  }
+  return MGENX_OK;
+}
+
+}  // extern "C"

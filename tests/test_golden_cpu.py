@@ -1,8 +1,11 @@
 """CPU: the oracle reproduces the committed golden vectors (tests/golden/udp_matrix.npz)
-and the C-ABI library loads and exports every symbol include/mgenx.h declares."""
+and the C-ABI library loads and exports every symbol include/mgenx.h declares, and no other
+C name."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -63,13 +66,34 @@ def _header_functions():
     return sorted(set(re.findall(r"\b(mgenx_[a-z0-9_]+)\s*\(", text)))
 
 
+def _exported_c_functions(path):
+    """The defined dynamic function symbols of a library whose names are C names of this
+    project (mgenx_*); mangled C++ names do not match."""
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True,
+                         text=True).stdout
+    names = set()
+    for line in out.splitlines():
+        f = line.split()
+        if len(f) == 3 and f[1] in "TtWw" and re.match(r"^mgenx_[a-z0-9_]+$", f[2]):
+            names.add(f[2])
+    return sorted(names)
+
+
 def test_capi_library_exports_header_symbols():
-    from mgen_amd import LIB_PATH, load
+    from mgen_amd import DIAG_LIB_PATH, DIAG_SYMBOLS, LIB_PATH, load
     assert os.path.exists(LIB_PATH), "libmgenx.so not built (run __graft_entry__.build())"
     lib = load()
     missing = [s for s in _header_functions() if not hasattr(lib, s)]
     assert not missing, missing
     assert lib.mgenx_abi_version() == 1
+    # and nothing else: a host function shared between the library's files is a C++ function
+    # of namespace mgenx (mgen_amd/csrc/mgenx_internal.hpp), not another C name
+    extra = sorted(set(_exported_c_functions(LIB_PATH)) - set(_header_functions()))
+    assert not extra, extra
+    assert _exported_c_functions(LIB_PATH) == _header_functions()
+    assert _exported_c_functions(DIAG_LIB_PATH) == sorted(_header_functions() +
+                                                          list(DIAG_SYMBOLS))
 
 
 def test_python_symbol_list_matches_header():
