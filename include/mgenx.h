@@ -724,7 +724,8 @@ int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32
  * records (columns dst_addr, dst_len, dst_port, flow_id, and err when given: err != 0 maps
  * to MGENX_FLOW_NONE) with their recvfrom source addresses to dev_flow_idx[i] -- the input
  * mgenx_flow_reduce takes -- and copies the table's flow count to dev_n_flows[0] (optional,
- * device memory).  Keys persist across calls (streaming batches).
+ * device memory).  Keys persist across calls (streaming batches).  An empty batch (n == 0)
+ * changes nothing and still reports the table's count to dev_n_flows, in stream order.
  * With cols->rows (the 32-B mgenx_rec output) the key fields and err come from the rows;
  * the destination address from the dst_addr column when given, else from the rows'
  * dst_addr4 -- exact for IPv4 destinations; a record whose dst_len exceeds 4 then maps to

@@ -1099,7 +1099,8 @@ class Engine:
         self.lib.mgenx_flow_table_destroy(t)
 
     def flow_lookup(self, table, cols, src, n, flow_idx=None, n_flows=None):
-        """Dense flow index per record (mgenx_flow_lookup); returns (flow_idx, n_flows)."""
+        """Dense flow index per record (mgenx_flow_lookup); returns (flow_idx, n_flows).
+        n_flows[0] is the table's flow count after the call, for an empty batch (n == 0) too."""
         torch = self.torch
         dev = src.device
         if flow_idx is None:

@@ -662,7 +662,14 @@ int mgenx_flow_lookup(mgenx_ctx* ctx, mgenx_flow_table* t, const mgenx_cols* col
                       const mgenx_addr* dev_src, uint32_t n, uint32_t* dev_flow_idx,
                       uint32_t* dev_n_flows, void* stream) {
   if (!ctx || !t || !cols) return MGENX_EINVAL;
-  if (n == 0) return MGENX_OK;
+  if (n == 0) {
+    // an empty batch changes nothing (parity and the n_new words stay) and still reports the
+    // table's count, in stream order after the calls before it
+    if (dev_n_flows && hipMemcpyAsync(dev_n_flows, t->counters, 4, hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream) != hipSuccess)
+      return MGENX_EDEVICE;
+    return MGENX_OK;
+  }
   const mgenx_cols& c = *cols;
   if (!c.rows && (!c.dst_addr || !c.dst_len || !c.dst_port || !c.flow_id)) return MGENX_EINVAL;
   if (!dev_src || !dev_flow_idx) return MGENX_EINVAL;
@@ -676,10 +683,10 @@ int mgenx_flow_lookup(mgenx_ctx* ctx, mgenx_flow_table* t, const mgenx_cols* col
   uint32_t* blk_cnt = (uint32_t*)take(bb);
   uint32_t* blk_base = (uint32_t*)take(bb);
   // n_new alternates between counters[3] and [4]: each call clears the word the next call
-  // counts in
+  // counts in (parity advances once nothing before the launches can fail any more: a call that
+  // fails leaves both words, and which of them counts, as they were)
   uint32_t* n_new = t->counters + 3 + (t->parity & 1u);
   uint32_t* n_new_next = t->counters + 3 + ((t->parity + 1u) & 1u);
-  t->parity++;
   int mode = 0;
 #if MGENX_DIAG
   if (const char* m = getenv("MGENX_FT_MODE")) mode = atoi(m);
@@ -688,6 +695,7 @@ int mgenx_flow_lookup(mgenx_ctx* ctx, mgenx_flow_table* t, const mgenx_cols* col
   if (t->cap <= kFtSmallCap) {
     hipError_t e = set_max_lds((const void*)flowtab_probe_kernel, (int)kFtLdsBytes);
     if (e != hipSuccess) return MGENX_EDEVICE;
+    t->parity++;
     // keys staged: up to kFtKeys (80 KB of LDS with the map: two workgroups per CU)
     uint32_t kcap = std::min(t->cap / 2u, kFtKeys), gmul = 2;
 #if MGENX_DIAG
@@ -705,6 +713,7 @@ int mgenx_flow_lookup(mgenx_ctx* ctx, mgenx_flow_table* t, const mgenx_cols* col
     return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
   }
   const uint32_t gs = std::min(nblk, kFtGrid), gf = std::min((n + 255u) / 256u, 4u * kFtGrid);
+  t->parity++;
   hipLaunchKernelGGL(flowtab_insert_kernel, dim3((n + 255) / 256), b, 0, s, t->slots, t->cap - 1,
                      c, dev_src, n, rec_slot, t->counters + 2, dev_flow_idx, n_new, t->counters);
   hipLaunchKernelGGL(flowtab_first_kernel, dim3(gs), bk, 0, s, t->slots, rec_slot, n, flag,
