@@ -194,3 +194,71 @@ def test_doc_tcp_fragment_example(oracle, checksum):
     text = oracle.log_recv_text(f, np.frombuffer(stream, np.uint8), offs, src, rx_sec, rx_usec,
                                 protocol=2).decode()
     assert text.splitlines(keepends=True) == doc_tcp_expected_lines()
+
+
+# doc/mgen.xml:4734-4737 (dstAddrLen is 4 for IPv4, 16 for IPv6), :4743-4745 (the message may
+# be truncated at any point after dstAddr; an incomplete optional field is invalid) and
+# :4834-4844 (minimum sizes 28 / 40 with no optional fields, 52 / 76 with the host address
+# and the GPS information untruncated), on or_pack and or_unpack.
+DOC_V4 = ("4", bytes([10, 1, 2, 3]), 5000)
+DOC_V6 = ("6", bytes(range(1, 17)), 7000)
+DOC_H4 = ("4", bytes([192, 168, 0, 9]), 4000)
+DOC_H6 = ("6", bytes(range(33, 49)), 4001)
+DOC_LAT_RAW = (10 + 180) * 60000
+
+
+def doc_size_msg(oracle, size, dst, host):
+    return oracle.make_msg(msg_len=size, flow_id=3, seq=9, tx_sec=1_700_000_000, tx_usec=5,
+                           dst=dst, host=host, lat=10.0, lon=20.0, alt=7, gps_status=2,
+                           payload_type=1)
+
+
+def doc_pack_unpack(oracle, size, dst, host):
+    ret, rec, _, _, hdr = oracle.pack(doc_size_msg(oracle, size, dst, host), size)
+    return ret, hdr, (oracle.unpack(rec[:ret]) if ret else None)
+
+
+@pytest.mark.parametrize("dst,dlen,minimum", [(DOC_V4, 4, 28), (DOC_V6, 16, 40)])
+def test_doc_minimum_size_no_optional_fields(oracle, dst, dlen, minimum):
+    ret, hdr, _ = doc_pack_unpack(oracle, minimum - 1, dst, None)
+    assert ret == 0                                   # Pack refuses one byte fewer
+    ret, hdr, f = doc_pack_unpack(oracle, minimum, dst, None)
+    assert ret == minimum and hdr == minimum
+    assert f["ok"] == 1 and f["err"] == 0 and f["hdr_len"] == minimum
+    assert f["dst_type"] == (1 if dlen == 4 else 2) and f["dst_len"] == dlen
+    assert bytes(f["dst_addr"][:dlen]) == dst[1] and f["dst_port"] == dst[2]
+    assert f["host_type"] == 0 and f["gps_status"] == 0 and f["lat_raw"] == 10800000
+    if dlen == 4:   # Unpack's own floor is MIN_SIZE = 28 whatever the address type
+        short = oracle.unpack(bytes(27))
+        assert short["ok"] == 0 and short["err"] == 3            # ERROR_LENGTH
+
+
+@pytest.mark.parametrize("dst,host,alen,full", [(DOC_V4, DOC_H4, 4, 52), (DOC_V6, DOC_H6, 16, 76)])
+def test_doc_minimum_size_with_host_and_gps(oracle, dst, host, alen, full):
+    """52 / 76 is the first size whose Unpack decodes payload_len; one byte fewer loses it,
+    four fewer lose the GPS block, and a size that cuts the host address loses the host."""
+    ret, hdr, f = doc_pack_unpack(oracle, full, dst, host)
+    assert ret == full and hdr == full and f["hdr_len"] == full and f["err"] == 0
+    assert f["dst_len"] == alen and f["host_len"] == alen          # 16 for IPv6 (:4734-4737)
+    assert f["host_type"] == (1 if alen == 4 else 2) and bytes(f["host_addr"][:alen]) == host[1]
+    assert f["host_port"] == host[2] and f["gps_status"] == 2 and f["payload_type"] == 1
+    assert f["lat_raw"] == DOC_LAT_RAW and f["alt"] == 7
+    for size in range(24 + alen + 4, full):
+        assert doc_pack_unpack(oracle, size, dst, host)[2]["hdr_len"] != full, size
+    # one byte fewer: GPS and payload type decoded, payload_len not (packet_header_len stays 0)
+    ret, _, f = doc_pack_unpack(oracle, full - 1, dst, host)
+    assert ret == full - 1 and f["ok"] == 1 and f["err"] == 0
+    assert f["gps_status"] == 2 and f["lat_raw"] == DOC_LAT_RAW and f["payload_type"] == 1
+    assert f["hdr_len"] == 0 and f["payload_len"] == 0 and f["host_len"] == alen
+    # four bytes fewer: the host address decoded, no GPS information
+    ret, hdr, f = doc_pack_unpack(oracle, full - 4, dst, host)
+    assert ret == full - 4 and hdr == 28 + 2 * alen and f["hdr_len"] == 28 + 2 * alen
+    assert f["host_type"] == (1 if alen == 4 else 2) and f["host_len"] == alen
+    assert bytes(f["host_addr"][:alen]) == host[1]
+    assert f["gps_status"] == 0 and f["lat_raw"] == 10800000 and f["alt"] == 0
+    # one byte short of the host address (35 / 59): no host
+    size = 28 + 2 * alen - 1
+    ret, hdr, f = doc_pack_unpack(oracle, size, dst, host)
+    assert ret == size and hdr == 24 + alen and f["ok"] == 1 and f["err"] == 0
+    assert f["host_type"] == 0 and f["host_len"] == 0 and f["host_port"] == 0
+    assert not f["host_addr"].any() and f["dst_len"] == alen
