@@ -569,7 +569,15 @@ int mgenx_flow_init(mgenx_ctx* ctx, mgenx_flow_state* dev_flows, uint32_t n_flow
  * record in dev_rx_sec/dev_rx_usec.  Reports go to dev_reports[f * per_flow + k] for
  * k < per_flow; dev_report_count[f] (zeroed by the caller) counts all of them.  With
  * per_flow == 0, dev_reports and dev_report_count may be NULL (the states' n_reports still
- * count every report).  Synchronous on `stream` only when its workspace must grow. */
+ * count every report).  Synchronous on `stream` only when its workspace must grow.
+ * Values: the four times are any uint32_t.  tx_usec and rx_usec are taken as they are, 10^6
+ * and more included: ProtoTime::Delta subtracts the fields widened to int64 (latencies of any
+ * sign and size), receive times compare by seconds, then microseconds, and only a window end
+ * is normalised (its seconds may pass 2^32: no record closes that window).  Receive times
+ * need not increase.  A window that quantizes to 0 (window_sec < 0.5 us) closes on every
+ * record after a flow's first, nothing is written past slot per_flow - 1 of a flow, and a
+ * duration of 0 gives the reference's inf and 0 / 0.  Where the oracle's double is NaN, the
+ * GPU's must be NaN of any sign or payload.  Everything else is byte-equal. */
 int mgenx_flow_reduce(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_seq,
                       const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
                       const uint16_t* dev_msg_len, const uint32_t* dev_rx_sec,

@@ -48,6 +48,18 @@ int mgenx_diag_group_rw(mgenx_ctx* ctx, const uint8_t* dev_data, uint64_t bytes,
  * restart cycles, restarts); n == 16 flow_order_kernel (8 entries). */
 int mgenx_diag_seg_prof(unsigned long long* out, int n);
 
+/* The ordering in front of mgenx_flow_reduce's update, forced (environment, read per call by
+ * this library only): MGENX_AN_RADIX=1 the radix sort; MGENX_AN_SCAN1=1 / 0 the counting sort's
+ * single-pass scan / its three kernels (colpart, colbase, colscan); MGENX_AN_TILE=4096 / 4608
+ * the tile size (4608 only where its LDS fits: n_flows <= 1222).
+ * MGENX_AN_C1_GIVEUP=M (M >= 1): blocks j > 0 of the single-pass scan with j mod M == M - 1 skip
+ * their look-back poll and take the give-up branch (the block sums the histogram itself); it
+ * shortens a wait and never lengthens one.  MGENX_AN_C1_WRAP=1: a context's first single-pass
+ * scan starts at epoch kC1Epochs - 2, so its third call restarts the epochs.
+ * mgenx_diag_c1_giveups: waits for the device, then *out = the blocks that took the give-up
+ * branch since the last call of this function (forced or not), and clears the count. */
+int mgenx_diag_c1_giveups(unsigned long long* out);
+
 /* Diagnostic: the resident worker's own time for its last Unpack / receive request, in 10-ns
  * ticks from the poll that saw it: header parsed, checksum done, reply stored; out[3] = the
  * request number they belong to; out[4], out[5] = shader clocks (s_memtime) to the parse and

@@ -66,7 +66,7 @@ EXPORTED_SYMBOLS = (
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
-                "mgenx_diag_chain_prof")
+                "mgenx_diag_chain_prof", "mgenx_diag_c1_giveups")
 
 
 class MgenxError(RuntimeError):
@@ -150,6 +150,7 @@ def load(diag: bool = False):
         L.mgenx_diag_stream_read_w.argtypes = [P, P, u64, P, i32, i32, P]
         L.mgenx_diag_worker_stamps.argtypes = [P, P]
         L.mgenx_diag_chain_prof.argtypes = [P]
+        L.mgenx_diag_c1_giveups.argtypes = [ctypes.POINTER(u64)]
     L.mgenx_stream_scan.argtypes = [P, P, u64, i32, P, P, u64, ctypes.POINTER(ScanInfo), P]
     L.mgenx_tcp_rx_persist.argtypes = [P, P, P, P, u32, P, P, P, u32, P]
     L.mgenx_report_build.argtypes = [P, P, u32, u32, P, P, P, P, P, P, P]

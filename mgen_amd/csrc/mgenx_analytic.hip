@@ -1120,15 +1120,27 @@ flow_colscan_kernel(const uint32_t* __restrict__ hist, const uint32_t* __restric
 // (epoch-tagged words: epoch << 40 | kind << 38 | count, kind 1 = the block's own total, 2 =
 // inclusive of every block before it), then start[] written down each segment.  Blocks wait
 // only on lower blocks, all resident (<= 96 blocks); a poll count bounds every wait anyway.
+// A block whose poll count runs out (the give-up branch) uses nothing of what it polled: it
+// sums hist over every tile for all flows below its own (at most 1520 x n_tiles loads over its
+// 256 threads), so its prefix, its inclusive word and start[] are right all the same, and the
+// blocks after it need not look further back than its word.  No host round trip: the call
+// stays asynchronous.  (Diagnostics build: force_m = M sends blocks j > 0 with j mod M == M - 1
+// there without polling -- it shortens a wait, never lengthens one -- and g_c1_gaveup counts
+// the blocks that took the branch.)
 constexpr uint32_t kC1Flows = 16, kC1Segs = 16;
 constexpr uint32_t kC1Epochs = 1u << 22;
 constexpr uint32_t kC1Spin = 1u << 20;
+#if MGENX_DIAG
+__device__ unsigned long long g_c1_gaveup;
+#endif
 __global__ void __launch_bounds__(256)
 flow_colscan1_kernel(const uint32_t* __restrict__ hist, uint32_t bins, uint32_t n_tiles,
-                     uint32_t* __restrict__ start, uint64_t* __restrict__ status, uint32_t epoch) {
+                     uint32_t* __restrict__ start, uint64_t* __restrict__ status, uint32_t epoch,
+                     uint32_t force_m) {
   __shared__ uint32_t part[kC1Segs][kC1Flows];
   __shared__ uint32_t fpre[kC1Flows];
-  __shared__ uint64_t s_excl;
+  __shared__ uint32_t red[4];
+  __shared__ uint64_t s_excl;  // the records of all lower flows; bit 63: the look-back gave up
   const uint32_t tid = threadIdx.x, lane = tid & 63u, kk = tid % kC1Flows, sg = tid / kC1Flows;
   const uint32_t j = blockIdx.x, k = j * kC1Flows + kk;
   const uint32_t per = (n_tiles + kC1Segs - 1u) / kC1Segs;
@@ -1175,7 +1187,7 @@ flow_colscan1_kernel(const uint32_t* __restrict__ hist, uint32_t bins, uint32_t 
       __hip_atomic_store(&status[j], ((uint64_t)epoch << 40) | ((uint64_t)(j == 0 ? 2u : 1u) << 38) | agg,
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint64_t acc = 0;
-    bool gave_up = false;
+    bool gave_up = force_m != 0u && j != 0u && j % force_m == force_m - 1u;
     for (int64_t top = (int64_t)j - 1; top >= 0 && !gave_up; top -= 64) {
       const int64_t q = top - (int64_t)lane;
       uint64_t w = 0;
@@ -1187,7 +1199,8 @@ flow_colscan1_kernel(const uint32_t* __restrict__ hist, uint32_t bins, uint32_t 
       }
       const bool here = q < 0 || (uint32_t)(w >> 40) == epoch;
       gave_up = __ballot(!here) != 0;
-      const uint32_t kind = q >= 0 ? (uint32_t)(w >> 38) & 3u : 2u;
+      // (kind and count only from a word of this epoch; below block 0 counts as inclusive)
+      const uint32_t kind = q < 0 ? 2u : here ? (uint32_t)(w >> 38) & 3u : 0u;
       const uint64_t v = q >= 0 && here ? (w & ((1ull << 38) - 1)) : 0ull;
       const uint64_t done = __ballot(kind == 2u);
       const uint32_t stop = done ? (uint32_t)__ffsll((long long)done) - 1u : 64u;
@@ -1198,16 +1211,37 @@ flow_colscan1_kernel(const uint32_t* __restrict__ hist, uint32_t bins, uint32_t 
       if (done) break;
     }
     if (lane == 0) {
-      if (j != 0)
+      if (j != 0 && !gave_up)
         __hip_atomic_store(&status[j], ((uint64_t)epoch << 40) | (2ull << 38) | (acc + agg),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_excl = acc;
+      s_excl = gave_up ? 1ull << 63 : acc;
     }
   }
   __syncthreads();
+  uint32_t excl = (uint32_t)s_excl;
+  if (s_excl >> 63) {  // (block-uniform) the records of all lower flows, from hist itself
+    const uint32_t below = j * kC1Flows;  // (< bins: j > 0 is a launched block)
+    uint32_t s = 0;
+    for (uint32_t t = 0; t < n_tiles; t++)
+      for (uint32_t fl = tid; fl < below; fl += 256u) s += hist[(size_t)t * bins + fl];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += (uint32_t)__shfl_xor((int)s, o);
+    if (lane == 0) red[tid >> 6] = s;
+    __syncthreads();
+    excl = red[0] + red[1] + red[2] + red[3];
+    if (tid == 0) {  // (the thread that stored the block's own total: kind 1, read back here)
+      const uint64_t own = __hip_atomic_load(&status[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&status[j], ((uint64_t)epoch << 40) | (2ull << 38) |
+                                         ((uint64_t)excl + (own & ((1ull << 38) - 1))),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if MGENX_DIAG
+      atomicAdd(&g_c1_gaveup, 1ull);
+#endif
+    }
+  }
   // 4. start[] down this thread's segment
   if (k < bins) {
-    uint32_t run = (uint32_t)s_excl + fpre[kk] + part[sg][kk];
+    uint32_t run = excl + fpre[kk] + part[sg][kk];
     uint32_t t = t0;
     for (; t + 8u <= t1; t += 8u) {
       uint32_t x[8];
@@ -1345,6 +1379,14 @@ extern "C" int mgenx_diag_seg_prof(unsigned long long* out, int n) {
                                                                               : MGENX_EDEVICE;
   return MGENX_EINVAL;
 }
+extern "C" int mgenx_diag_c1_giveups(unsigned long long* out) {
+  const unsigned long long zero = 0;
+  if (!out || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpyFromSymbol(out, HIP_SYMBOL(g_c1_gaveup), 8) != hipSuccess ||
+      hipMemcpyToSymbol(HIP_SYMBOL(g_c1_gaveup), &zero, 8) != hipSuccess)
+    return out ? MGENX_EDEVICE : MGENX_EINVAL;
+  return MGENX_OK;
+}
 #endif
 
 int mgenx::flow_init_run(mgenx_flow_state* flows, uint32_t n_flows, double window,
@@ -1453,8 +1495,11 @@ int mgenx::flow_reduce_run(mgenx_flow_ws* wsp, const uint32_t* flow_idx, const u
     // (228 tiles: 0.1259 vs 0.1287 ms, three A/B pairs) but not config 4's 2048 tiles (0.2620
     // vs 0.2587)
     bool one = n_tiles <= 512u;
+    uint32_t c1_force = 0, c1_first = 1;  // diagnostics build only: see mgenx_diag.h
 #if MGENX_DIAG
     if (const char* c1 = getenv("MGENX_AN_SCAN1")) one = atoi(c1) != 0;  // (A/B)
+    if (const char* gu = getenv("MGENX_AN_C1_GIVEUP")) c1_force = (uint32_t)max(0, atoi(gu));
+    if (const char* ew = getenv("MGENX_AN_C1_WRAP")) c1_first = atoi(ew) ? kC1Epochs - 2u : 1u;
 #endif
     if (one) {
       if (!ws.c1_status) {
@@ -1465,15 +1510,16 @@ int mgenx::flow_reduce_run(mgenx_flow_ws* wsp, const uint32_t* flow_idx, const u
         }
         ws.c1_epoch = 0;
       }
-      if (ws.c1_epoch == 0 || ++ws.c1_epoch >= kC1Epochs) {  // (re)start the epochs from zeros
+      const bool fresh = ws.c1_epoch == 0;
+      if (fresh || ++ws.c1_epoch >= kC1Epochs) {  // (re)start the epochs from zeros
         if (hipMemsetAsync(ws.c1_status, 0, (kCountBins / kC1Flows + 1) * 8, stream) != hipSuccess) {
           snprintf(err, errn, "flow_reduce: scan words");
           return MGENX_EDEVICE;
         }
-        ws.c1_epoch = 1;
+        ws.c1_epoch = fresh ? c1_first : 1u;
       }
       hipLaunchKernelGGL(flow_colscan1_kernel, dim3((bins + kC1Flows - 1u) / kC1Flows), dim3(256), 0,
-                         stream, hist, bins, n_tiles, start, ws.c1_status, ws.c1_epoch);
+                         stream, hist, bins, n_tiles, start, ws.c1_status, ws.c1_epoch, c1_force);
     } else {
       const uint32_t n_chunks = (n_tiles + kColTiles - 1u) / kColTiles;
       const dim3 cg((bins + 255u) / 256u, n_chunks);
