@@ -11,7 +11,8 @@
  * scratch grow it (hipMalloc) the first time a larger batch arrives -- warm them up with
  * the largest batch before capturing a graph.  The log / report / walk formatters keep
  * one workspace per stream; the stream scans, mgenx_flow_reduce, mgenx_flow_dist,
- * mgenx_flow_series, mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per context, so those run on one stream
+ * mgenx_flow_series, mgenx_flow_series_quantiles, mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per
+ * context, so those run on one stream
  * at a time per context (one context per concurrent stream).
  *
  * Return value: 0 = launched, <0 = argument/launch error (MGENX_E*).  Per-record
@@ -36,6 +37,7 @@
  *                       the manual reads logs for (doc/mgen.xml:3399-3450)
  *   mgenx_flow_series   no reference code: rate, loss, latency and jitter per flow and window
  *                       of receive time, what the manual plots with trpr (doc/mgen.xml:3452-3457)
+ *   mgenx_flow_series_quantiles   no reference code: the exact latency percentiles of those windows
  */
 #ifndef MGENX_H
 #define MGENX_H
@@ -723,6 +725,43 @@ int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32
                       const uint32_t* dev_rx_usec, uint32_t n, int64_t t0_us, uint64_t width_us,
                       uint32_t n_bins, struct mgenx_flow_series_state* dev_state,
                       struct mgenx_flow_series_bin* dev_bins, uint32_t n_flows, void* stream);
+
+/* ---- per-flow time series: exact latency percentiles per window ----
+ * p50 / p95 / p99 over time: per flow and window of receive time, the exact order statistics of
+ * the latency.  No reference code: the definition below is the contract.  Integer arithmetic;
+ * the result is a pure function of the inputs, whatever order the workgroups finish in.
+ *
+ * Records i < n with dev_flow_idx[i] < n_flows count (others are skipped, MGENX_FLOW_NONE
+ * included).  rx and lat are mgenx_flow_dist's (signed 64-bit, the u32 columns widened first, a
+ * tx_usec >= 10^6 taken as it is) and the bin is mgenx_flow_series's:
+ *   b = floor((rx - t0_us) / width_us), a signed floor
+ * A record whose b lies outside [0, n_bins) belongs to no cell and is ignored; there is no
+ * per-flow state.  Cell (f, b) holds the multiset of lat of its records: duplicates count
+ * separately and the receive order plays no part.  With c the cell's size and permille[j] = q in
+ * 1..1000 (host array), r = max(1, (q * c + 999) / 1000) in unsigned 64-bit division -- the rank
+ * rule of mgenx_flow_dist_quantiles -- and
+ *   dev_out[(f * n_bins + b) * n_q + j] = the r-th smallest lat of the cell,
+ * exact: negative latencies in their signed order, no clamping at 2^32.  INT64_MIN for an empty
+ * cell.  Every element of dev_out [n_flows * n_bins * n_q] is written on every call and nothing
+ * beyond it; n == 0 fills it with INT64_MIN; n_flows == 0 touches nothing and returns MGENX_OK.
+ * Not streaming, by design: an exact order statistic needs every value of its cell, so one call
+ * takes the whole log, as mgenx_msg_match does.
+ * MGENX_EINVAL (found before any HIP call): a null ctx; width_us == 0; n_bins == 0; n_q == 0 or
+ * n_q > MGENX_FLOW_SERIES_MAX_Q; a permille outside 1..1000; a null permille or dev_out; a null
+ * column with n > 0; n >= 2^31; n_flows * n_bins >= 2^31.
+ * Workspace: owned by the context and grown when needed; the call is synchronous on `stream`
+ * only when it grows.  With C = n_flows * n_bins its size is, each piece rounded up to 256 B,
+ *   36 n + 4 (C + 1) + the radix sort's temporary storage for n pairs           (grouping)
+ *   + 4 (min(C, n/9) + min(C, n/257) + min(C, n/2049) + min(C, n/16385)) + 16   (tier lists)
+ *   + min(C, n/16385) * 32 * (8 + 4 + 1024)            (radix select over cells above 16384)
+ * bytes.  Asynchronous otherwise; one such call per context at a time. */
+#define MGENX_FLOW_SERIES_MAX_Q 32
+int mgenx_flow_series_quantiles(mgenx_ctx* ctx, const uint32_t* dev_flow_idx,
+                                const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                                const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec, uint32_t n,
+                                int64_t t0_us, uint64_t width_us, uint32_t n_bins,
+                                uint32_t n_flows, const uint32_t* permille, uint32_t n_q,
+                                int64_t* dev_out, void* stream);
 
 
 /* ---- MgenAnalyticTable::FindFlow for batches (mgenAnalytic.cpp:312-328) ----

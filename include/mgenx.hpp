@@ -721,6 +721,40 @@ class FlowSeries {
   DeviceArray<uint32_t> d_idx_, d_rxs_, d_rxu_;
 };
 
+// ---- per-flow time series: exact latency percentiles per window ----------------------------
+// mgenx_flow_series_quantiles over one decoded batch (include/mgenx.h): for window b of flow f
+// and permille[j], element (f * nBins + b) * permille.size() + j of the result is the exact
+// order statistic of the window's latencies, INT64_MIN for a window without records.  One shot:
+// an exact percentile needs every record of its window, so the batch is the whole log.
+inline std::vector<int64_t> FlowSeriesQuantiles(Context& ctx, const RecvBatch& b,
+                                                const std::vector<uint32_t>& flowIdx,
+                                                const std::vector<uint32_t>& rxSec,
+                                                const std::vector<uint32_t>& rxUsec,
+                                                uint32_t nFlows, int64_t t0_us, uint64_t width_us,
+                                                uint32_t nBins,
+                                                const std::vector<uint32_t>& permille) {
+  const uint32_t n = b.Size();
+  const size_t cells = (size_t)nFlows * nBins * permille.size();
+  DeviceArray<uint32_t> d_idx(n), d_rxs(n), d_rxu(n);
+  DeviceArray<int64_t> d_out(cells);
+  hipStream_t s = ctx.stream();
+  if (n) {
+    check_hip(hipMemcpyAsync(d_idx.data(), flowIdx.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxs.data(), rxSec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+    check_hip(hipMemcpyAsync(d_rxu.data(), rxUsec.data(), n * 4, hipMemcpyHostToDevice, s), "H2D");
+  }
+  ctx.Check(mgenx_flow_series_quantiles(ctx.get(), d_idx.data(), b.DevTxSec(), b.DevTxUsec(),
+                                        d_rxs.data(), d_rxu.data(), n, t0_us, width_us, nBins,
+                                        nFlows, permille.data(), (uint32_t)permille.size(),
+                                        d_out.data(), s),
+            "mgenx_flow_series_quantiles");
+  std::vector<int64_t> out(cells);
+  if (cells)
+    check_hip(hipMemcpyAsync(out.data(), d_out.data(), cells * 8, hipMemcpyDeviceToHost, s), "D2H");
+  ctx.Sync();
+  return out;
+}
+
 // ---- a sender's log joined with a receiver's log: per-message loss ---------------------------
 // mgenx_msg_match (include/mgenx.h) over host columns: the sender's records (flow index, seq, the
 // SEND stamp, size) and the receiver's (flow index, seq, sent> stamp, receive time), with flow

@@ -59,7 +59,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcapng_index", "mgenx_pcapng_parse", "mgenx_pcapng_snap",
     "mgenx_flow_dist_init", "mgenx_flow_dist", "mgenx_flow_dist_quantiles",
     "mgenx_flow_dist_bin", "mgenx_flow_dist_bin_lo",
-    "mgenx_flow_series_init", "mgenx_flow_series",
+    "mgenx_flow_series_init", "mgenx_flow_series", "mgenx_flow_series_quantiles",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
     "mgenx_match_side", "mgenx_msg_match",
@@ -173,6 +173,8 @@ def load(diag: bool = False):
     L.mgenx_flow_series_init.argtypes = [P, P, P, u32, u32, P]
     L.mgenx_flow_series.argtypes = [P, P, P, P, P, P, P, P, u32, ctypes.c_int64, u64, u32, P, P,
                                     u32, P]
+    L.mgenx_flow_series_quantiles.argtypes = [P, P, P, P, P, P, u32, ctypes.c_int64, u64, u32, u32,
+                                              ctypes.POINTER(u32), u32, P, P]
     L.mgenx_match_side.argtypes = [P, P, P, P, u32, u32, P, P, P]
     L.mgenx_msg_match.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P, P,
                                   P, P, P]
@@ -685,6 +687,24 @@ class Engine:
                                                _ptr(rx_usec), n, int(t0_us), int(width_us),
                                                int(n_bins), _ptr(state), _ptr(bins), n_flows,
                                                _stream(self.device)), "mgenx_flow_series")
+
+    def flow_series_quantiles(self, n_flows, n_bins, t0_us, width_us, permille, flow_idx, tx_sec,
+                              tx_usec, rx_sec, rx_usec, n=None, out=None):
+        """Exact latency percentiles per flow and window (mgenx_flow_series_quantiles): an int64
+        tensor [n_flows, n_bins, len(permille)], the r-th smallest latency of each cell with
+        mgenx_flow_dist_quantiles' rank rule, INT64_MIN for an empty cell.  One call takes the
+        whole log; `out` may pass a tensor of that many elements to write into."""
+        torch = self.torch
+        n = flow_idx.numel() if n is None else n
+        q = (ctypes.c_uint32 * len(permille))(*[int(v) for v in permille])
+        if out is None:
+            out = torch.empty((n_flows, n_bins, len(permille)), dtype=torch.int64,
+                              device=f"cuda:{self.device}")
+        self._check(self.lib.mgenx_flow_series_quantiles(
+            self.ctx, _ptr(flow_idx), _ptr(tx_sec), _ptr(tx_usec), _ptr(rx_sec), _ptr(rx_usec),
+            n, int(t0_us), int(width_us), int(n_bins), n_flows, q, len(permille), _ptr(out),
+            _stream(self.device)), "mgenx_flow_series_quantiles")
+        return out
 
     def match_side(self, parsed, n, want_event):
         """A parsed log (log_parse_text) made ready for flow_lookup as one side of msg_match
@@ -1296,14 +1316,19 @@ def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
 
 
 def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_base=0,
-                            device=0) -> tuple:
+                            device=0, permille=None) -> tuple:
     """Per-flow time series of an MGEN text log, on the GPU: line index -> parse -> FindFlow ->
     mgenx_flow_series.  Returns (keys, state, bins, t0_us, n_lines, n_malformed): numpy arrays
     of REPORT_KEY_DTYPE, FLOW_SERIES_STATE_DTYPE and FLOW_SERIES_BIN_DTYPE [n_flows, n_bins],
     flows in analyze_text_log's order.  By default t0_us is the lowest receive time among the
-    counted records and n_bins just enough to hold the highest (mgenx_flow_span)."""
+    counted records and n_bins just enough to hold the highest (mgenx_flow_span).  With
+    `permille` (values in 1..1000) the same parse also feeds mgenx_flow_series_quantiles and the
+    tuple gains a seventh element: the exact latency percentiles, int64 [n_flows, n_bins,
+    len(permille)]."""
     import torch
     width_us = int(width_us)
+    if permille is not None:
+        permille = tuple(int(q) for q in permille)
     if width_us < 1:
         raise ValueError("width_us must be at least 1")
     eng = Engine(device)
@@ -1314,9 +1339,12 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
         line_off, n = eng.text_index(text)
 
         def empty(n_lines, n_bad):
-            return (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_SERIES_STATE_DTYPE),
-                    np.zeros((0, n_bins or 1), FLOW_SERIES_BIN_DTYPE),
-                    0 if t0_us is None else int(t0_us), n_lines, n_bad)
+            r = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_SERIES_STATE_DTYPE),
+                 np.zeros((0, n_bins or 1), FLOW_SERIES_BIN_DTYPE),
+                 0 if t0_us is None else int(t0_us), n_lines, n_bad)
+            if permille is not None:
+                r += (np.zeros((0, n_bins or 1, len(permille)), np.int64),)
+            return r
         if n == 0:
             return empty(0, 0)
         p = eng.log_parse_text(text, line_off, n, day_base=day_base)
@@ -1336,14 +1364,22 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
         state, bins = eng.flow_series_init(nf, n_bins)
         eng.flow_series(state, bins, nf, n_bins, t0_us, width_us, flow_idx, p["seq_num"],
                         p["tx_sec"], p["tx_usec"], p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+        quant = None
+        if permille is not None:
+            quant = eng.flow_series_quantiles(nf, n_bins, t0_us, width_us, permille, flow_idx,
+                                              p["tx_sec"], p["tx_usec"], p["rx_sec"],
+                                              p["rx_usec"], n=n)
         recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
         proto = int(p["protocol"][recv][0].item())
         keys = eng.flow_keys(table, nf, protocol=proto)
         torch.cuda.synchronize(device)
-        return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
-                state.cpu().numpy().view(FLOW_SERIES_STATE_DTYPE).copy(),
-                bins.cpu().numpy().view(FLOW_SERIES_BIN_DTYPE).reshape(nf, n_bins).copy(),
-                t0_us, n, n_bad)
+        res = (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
+               state.cpu().numpy().view(FLOW_SERIES_STATE_DTYPE).copy(),
+               bins.cpu().numpy().view(FLOW_SERIES_BIN_DTYPE).reshape(nf, n_bins).copy(),
+               t0_us, n, n_bad)
+        if quant is not None:
+            res += (quant.cpu().numpy(),)
+        return res
     finally:
         if table is not None:
             eng.flow_table_destroy(table)

@@ -389,6 +389,28 @@ int mgenx_flow_series(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32
                                sizeof(ctx->err));
 }
 
+int mgenx_flow_series_quantiles(mgenx_ctx* ctx, const uint32_t* dev_flow_idx,
+                                const uint32_t* dev_tx_sec, const uint32_t* dev_tx_usec,
+                                const uint32_t* dev_rx_sec, const uint32_t* dev_rx_usec, uint32_t n,
+                                int64_t t0_us, uint64_t width_us, uint32_t n_bins,
+                                uint32_t n_flows, const uint32_t* permille, uint32_t n_q,
+                                int64_t* dev_out, void* stream) {
+  if (!ctx || width_us == 0 || n_bins == 0 || n_q == 0 || n_q > MGENX_FLOW_SERIES_MAX_Q ||
+      !permille || (uint64_t)n_flows * n_bins >= (1ull << 31))
+    return MGENX_EINVAL;
+  for (uint32_t j = 0; j < n_q; j++)
+    if (permille[j] < 1u || permille[j] > 1000u) return MGENX_EINVAL;
+  if (!dev_out || n > 0x7FFFFFFFu) return MGENX_EINVAL;
+  if (n && (!dev_flow_idx || !dev_tx_sec || !dev_tx_usec || !dev_rx_sec || !dev_rx_usec))
+    return MGENX_EINVAL;
+  if (n_flows == 0) return MGENX_OK;
+  hipSetDevice(ctx->device);
+  return mgenx::flow_quant_run(ctx->flowquant_ws, ctx->cu_count, dev_flow_idx, dev_tx_sec,
+                              dev_tx_usec, dev_rx_sec, dev_rx_usec, n, t0_us, width_us, n_bins,
+                              n_flows, permille, n_q, dev_out, (hipStream_t)stream, ctx->err,
+                              sizeof(ctx->err));
+}
+
 int mgenx_match_side(mgenx_ctx* ctx, const uint8_t* dev_event, const uint8_t* dev_status,
                      const mgenx_addr* dev_src, uint32_t n, uint32_t want_event,
                      mgenx_addr* dev_src_out, uint8_t* dev_err_out, void* stream) {

@@ -191,6 +191,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   if (c->flow_ws) mgenx::flow_ws_free(c->flow_ws);
   c->flowdist_ws.release();
   c->flowseries_ws.release();
+  c->flowquant_ws.release();
   c->match_ws.release();
   if (c->log_ws) mgenx::log_ws_free(c->log_ws);
   c->tcp_ws.release();

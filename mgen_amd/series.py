@@ -1,6 +1,6 @@
 """Per-flow time series of an MGEN receiver log as a table to plot.
 
-    python -m mgen_amd.series <log> <width_sec> [outfile]
+    python -m mgen_amd.series [-q 500,950,990] <log> <width_sec> [outfile]
 
 reads a text log, reduces it on the GPU (analyze_text_log_series: mgenx_flow_series, one time
 axis for all flows) and writes, per flow, a comment line and one row per non-empty window:
@@ -12,12 +12,18 @@ Two blank lines separate the flows, which is what gnuplot takes as the boundary 
 sets (`plot "f" index 2 using ($1/1e6):($3*8/width)`).  The columns are the integers of struct
 mgenx_flow_series_bin: rate = bytes / width, loss as seen in the window = advance - fresh, taken
 back later = late, mean latency = lat_sum / n, mean jitter = jitter_sum / n.
+
+-q takes a comma-separated list of permille values in 1..1000 (at most 32), before or after the
+positional arguments, and appends one column per value, lat_p500 lat_p950 lat_p990 for the list
+above: the window's exact latency percentiles (mgenx_flow_series_quantiles, the rank rule of
+mgenx_flow_dist_quantiles).  Rows exist only for non-empty windows, so every value is a latency.
 """
 from __future__ import annotations
 
 import ipaddress
 import sys
 
+MAX_Q = 32   # MGENX_FLOW_SERIES_MAX_Q
 COLUMNS = ("bin_start_us", "n", "bytes", "fresh", "late", "advance", "lat_min", "lat_max",
            "lat_sum", "jitter_sum")
 
@@ -34,32 +40,68 @@ def _addr(a) -> str:
     return "%s/%d" % (host, int(a["port"]))
 
 
-def format_series(keys, bins, t0_us, width_us) -> str:
+def parse_permille(text) -> tuple:
+    """The argument of -q: "500,950,990" -> (500, 950, 990).  ValueError for an empty list, more
+    than MAX_Q values, anything that is not a decimal integer, or a value outside 1..1000."""
+    parts = str(text).split(",")
+    if not 1 <= len(parts) <= MAX_Q:
+        raise ValueError("-q takes 1 to %d permille values" % MAX_Q)
+    out = []
+    for p in parts:
+        if not (p.isascii() and p.isdigit()):
+            raise ValueError("-q: %r is not a permille value" % p)
+        v = int(p)
+        if not 1 <= v <= 1000:
+            raise ValueError("-q: %d is outside 1..1000" % v)
+        out.append(v)
+    return tuple(out)
+
+
+def format_series(keys, bins, t0_us, width_us, quant=None, permille=()) -> str:
     """The table described above.  keys: REPORT_KEY_DTYPE [n_flows]; bins: FLOW_SERIES_BIN_DTYPE
-    [n_flows, n_bins].  Integers only: no value passes through a float."""
+    [n_flows, n_bins]; quant: None, or int64 [n_flows, n_bins, len(permille)] for the columns
+    lat_p<permille>.  Integers only: no value passes through a float."""
     t0_us, width_us = int(t0_us), int(width_us)
+    columns = COLUMNS
+    if quant is not None:
+        columns = COLUMNS + tuple("lat_p%d" % int(q) for q in permille)
     out = []
     for f in range(len(keys)):
         k = keys[f]
         lines = ["# flow>%d src>%s dst>%s" % (int(k["flow_id"]), _addr(k["src"]), _addr(k["dst"])),
-                 "# " + " ".join(COLUMNS)]
+                 "# " + " ".join(columns)]
         row = bins[f]
         for b in range(len(row)):
             e = row[b]
             if int(e["n"]) == 0:
                 continue
-            lines.append(" ".join(str(v) for v in (
-                t0_us + b * width_us, int(e["n"]), int(e["bytes"]), int(e["fresh"]),
-                int(e["late"]), int(e["advance"]), int(e["lat_min"]), int(e["lat_max"]),
-                int(e["lat_sum"]), int(e["jitter_sum"]))))
+            vals = (t0_us + b * width_us, int(e["n"]), int(e["bytes"]), int(e["fresh"]),
+                    int(e["late"]), int(e["advance"]), int(e["lat_min"]), int(e["lat_max"]),
+                    int(e["lat_sum"]), int(e["jitter_sum"]))
+            if quant is not None:
+                vals += tuple(int(quant[f][b][j]) for j in range(len(permille)))
+            lines.append(" ".join(str(v) for v in vals))
         out.append("\n".join(lines) + "\n")
     return "\n\n".join(out)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else argv
+    argv = list(sys.argv[1:] if argv is None else argv)
+    usage = "usage: python -m mgen_amd.series [-q 500,950,990] <log> <width_sec> [outfile]\n"
+    permille = None
+    if "-q" in argv:
+        at = argv.index("-q")
+        if at + 1 >= len(argv) or "-q" in argv[at + 2:]:
+            sys.stderr.write(usage)
+            return 2
+        try:
+            permille = parse_permille(argv[at + 1])
+        except ValueError as e:
+            sys.stderr.write("series: %s\n" % e)
+            return 2
+        del argv[at:at + 2]
     if len(argv) not in (2, 3):
-        sys.stderr.write("usage: python -m mgen_amd.series <log> <width_sec> [outfile]\n")
+        sys.stderr.write(usage)
         return 2
     from fractions import Fraction
     width_us = int(Fraction(argv[1]) * 10**6)
@@ -69,8 +111,13 @@ def main(argv=None) -> int:
     from . import analyze_text_log_series
     with open(argv[0], "rb") as fh:
         log = fh.read()
-    keys, _state, bins, t0_us, n_lines, n_bad = analyze_text_log_series(log, width_us)
-    text = format_series(keys, bins, t0_us, width_us)
+    if permille is None:
+        keys, _state, bins, t0_us, n_lines, n_bad = analyze_text_log_series(log, width_us)
+        text = format_series(keys, bins, t0_us, width_us)
+    else:
+        keys, _state, bins, t0_us, n_lines, n_bad, quant = analyze_text_log_series(
+            log, width_us, permille=permille)
+        text = format_series(keys, bins, t0_us, width_us, quant, permille)
     if len(argv) == 3:
         with open(argv[2], "w") as fh:
             fh.write(text)
