@@ -11,14 +11,14 @@ NAMES := mgenx_api mgenx_ctx mgenx_unpack mgenx_unpack_fixed mgenx_probe \
          mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_binlog mgenx_comm mgenx_worker \
          mgenx_worker_host mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse \
          mgenx_flowdist mgenx_defrag mgenx_pcap_tcp mgenx_flowseries mgenx_match \
-         mgenx_flowquant
+         mgenx_flowquant mgenx_flowclock
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_internal.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
        mgen_amd/csrc/mgenx_unpack_long.hpp mgen_amd/csrc/mgenx_flowsm.hpp \
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \
        mgen_amd/csrc/mgenx_flowdist.hpp mgen_amd/csrc/mgenx_capture.hpp \
-       mgen_amd/csrc/mgenx_flowquant.hpp
+       mgen_amd/csrc/mgenx_flowquant.hpp mgen_amd/csrc/mgenx_flowclock.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))
 DOBJ := $(addprefix build/diag/,$(addsuffix .o,$(NAMES)))
 LIBS := -L/opt/rocm/lib -lrccl -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
@@ -28,7 +28,7 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/shard_scan tools/pcap2mgen tests/cpp/logparse_host \
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
      tests/cpp/flow_series_host tests/cpp/msg_match_host tests/cpp/flow_quant_host \
-     tests/cpp/flow_quant_arith_host
+     tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -116,6 +116,17 @@ tests/cpp/flow_series_host: tests/cpp/flow_series_host.cpp include/mgenx.hpp inc
 
 # mgenx::FlowSeriesQuantiles over a decoded batch against a serial loop with std::sort
 tests/cpp/flow_quant_host: tests/cpp/flow_quant_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
+	$(HOSTCXX) $< -o $@ $(HOSTLD)
+
+# the point, key, side, floored-line and stamp arithmetic of mgenx_flow_clock (mgenx_flowclock.hpp)
+# as a stand-alone host program under the address and undefined-behaviour sanitizers
+# (tests/test_flow_clock_cpu.py); no HIP, no GPU
+tests/cpp/flow_clock_arith_host: tests/cpp/flow_clock_arith_host.cpp mgen_amd/csrc/mgenx_flowclock.hpp include/mgenx.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Iinclude $< -o $@
+
+# mgenx::FlowClock over a decoded batch against a serial monotone chain in the program
+tests/cpp/flow_clock_host: tests/cpp/flow_clock_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
 	$(HOSTCXX) $< -o $@ $(HOSTLD)
 
 # mgenx::MessageMatch over a sender's and a receiver's records against a serial loop in the program

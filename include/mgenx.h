@@ -11,7 +11,7 @@
  * scratch grow it (hipMalloc) the first time a larger batch arrives -- warm them up with
  * the largest batch before capturing a graph.  The log / report / walk formatters keep
  * one workspace per stream; the stream scans, mgenx_flow_reduce, mgenx_flow_dist,
- * mgenx_flow_series, mgenx_flow_series_quantiles, mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per
+ * mgenx_flow_series, mgenx_flow_series_quantiles, mgenx_flow_clock, mgenx_pack_tcp and mgenx_tcp_rx_persist keep one per
  * context, so those run on one stream
  * at a time per context (one context per concurrent stream).
  *
@@ -38,6 +38,8 @@
  *   mgenx_flow_series   no reference code: rate, loss, latency and jitter per flow and window
  *                       of receive time, what the manual plots with trpr (doc/mgen.xml:3452-3457)
  *   mgenx_flow_series_quantiles   no reference code: the exact latency percentiles of those windows
+ *   mgenx_flow_clock    no reference code: per-flow clock offset and skew removed from the
+ *                       one-way latencies (Moon, Skelly, Towsley, INFOCOM 1999)
  */
 #ifndef MGENX_H
 #define MGENX_H
@@ -762,6 +764,83 @@ int mgenx_flow_series_quantiles(mgenx_ctx* ctx, const uint32_t* dev_flow_idx,
                                 int64_t t0_us, uint64_t width_us, uint32_t n_bins,
                                 uint32_t n_flows, const uint32_t* permille, uint32_t n_q,
                                 int64_t* dev_out, void* stream);
+
+/* ---- per-flow clock offset and skew removal for one-way latencies ----
+ * Every latency above is rx - tx, two stamps from two hosts' clocks: a receiver clock that is
+ * off by milliseconds or drifts by tens of ppm shows up in every histogram and percentile.
+ * The remedy is Moon, Skelly and Towsley, "Estimation and removal of clock skew from network
+ * delay measurements" (INFOCOM 1999): per flow, the straight line that lies under every
+ * (send time, latency) point and is closest to the points is the clock offset plus skew plus
+ * the minimum path delay; what remains above it is queueing and jitter.  No reference code: the
+ * definition below is the contract.  Integer arithmetic, exact for every input; the result is a
+ * pure function of the inputs, whatever order the workgroups finish in.
+ *
+ * Records i < n with dev_flow_idx[i] < n_flows count (others are skipped, MGENX_FLOW_NONE
+ * included).  In 64-bit, the u32 columns widened first and a tx_usec >= 10^6 taken as it is:
+ *   x_i = tx_sec * 10^6 + tx_usec                              (unsigned, below 2^52)
+ *   d_i = (rx_sec - tx_sec) * 10^6 + rx_usec - tx_usec         (signed: mgenx_flow_dist's lat)
+ * The fit, per flow, over the set of its points (x_i, d_i).  H is the lower convex hull of the
+ * set: vertices in increasing x; among equal x only the lowest d can be a vertex; a point
+ * collinear with its hull neighbours is not a vertex.  S is the sum of x_i over the flow's n
+ * counted records as an exact integer.  With at least two distinct x, A and B are the
+ * consecutive vertices of H with n * x_A <= S < n * x_B: the hull edge over the mean send time
+ * (the edge that starts at the mean when the mean falls on a vertex).  Among all lines that
+ * pass under every point it minimises the sum of d_i - line(x_i).  With all x equal (n = 1
+ * included) A = B = (x, the lowest d).  With MGENX_CLOCK_OFFSET_ONLY the slope is forced to 0:
+ * A = B = the point of lowest d, of lowest x among those.  ia / ib: the lowest record index i
+ * whose point equals A / B.
+ *   line(x) = d_A + floor((d_B - d_A) * (x - x_A) / (x_B - x_A))     (d_A when x_A = x_B)
+ * with the mathematical floor (toward -inf) and x - x_A signed, and
+ *   c_i = d_i - line(x_i)
+ * c_i >= 0, and 0 at A and B.  Products reach 2^106: the arithmetic is 128-bit.  c_i is kept
+ * modulo 2^64 as a signed value; it leaves 63 bits only where the chosen edge is steeper than
+ * 2^11 us per us and the flow's send times reach further than 2^63 / that slope from it.
+ * Outputs; every element of every array given is written on every call and nothing beyond it:
+ *   dev_flows [n_flows]   struct mgenx_flow_clock (64 B): n; A = (xa, da), B = (xb, db); ia, ib;
+ *                         resid_sum = sum of c_i (wraps), resid_max = max c_i.  An empty flow:
+ *                         n = 0, xa = xb = 0, da = db = 0, resid_sum = 0, resid_max =
+ *                         INT64_MIN, ia = ib = MGENX_CLOCK_NONE.  No skew figure: floor(10^9 *
+ *                         (db - da) / (xb - xa)) does not fit 64 bits for every input; callers
+ *                         derive it from A and B.
+ *   dev_resid [n]         optional: c_i; INT64_MIN for a skipped record.
+ *   dev_rx_sec_out, dev_rx_usec_out [n]   optional, both or neither: the receive stamp on the
+ *                         sender's clock with the floor removed: with r = x_i + c_i, sec =
+ *                         (r / 10^6) mod 2^32 and usec = r mod 10^6; a skipped record gets its
+ *                         input stamp.  mgenx_flow_dist, mgenx_flow_series and
+ *                         mgenx_flow_series_quantiles fed these two columns in place of rx_*
+ *                         compute their statistics of c_i with no change of their own.  They
+ *                         must not overlap the input columns.
+ * dev_flow_idx may be any dense grouping: one index per sender host fits one clock per host.
+ * One call takes the whole log; it does not stream (a later record can lower the hull
+ * anywhere), as mgenx_msg_match does not.  n == 0 writes the empty structs; n_flows == 0
+ * touches nothing and returns MGENX_OK.
+ * MGENX_EINVAL (found before any HIP call): a null ctx or dev_flows; a null column with n > 0;
+ * only one of the two stamp outputs; unknown opts bits; n >= 2^31 or n_flows >= 2^31.
+ * Workspace: owned by the context and grown when needed; the call is synchronous on `stream`
+ * only when it grows.  Its size is, each piece rounded up to 256 B,
+ *   16 n + 4 (n_flows + 1) + the radix sort's temporary storage for n pairs     (grouping)
+ *   + 32 n                                      (the points, in input order and by flow)
+ *   + 4 + 4 min(n_flows, n / 2049)                     (the flows served by a workgroup)
+ * bytes.  Asynchronous otherwise; one such call per context at a time.
+ * Cost: a flow's fit reads its points once per round of the hull search (4-7 rounds on drift
+ * plus delay noise, more when every point is a hull vertex), a flow of more than 2048 points on
+ * one workgroup: a single flow of millions of records is the slow case. */
+#define MGENX_CLOCK_NONE        0xFFFFFFFFu
+#define MGENX_CLOCK_OFFSET_ONLY 0x1u
+struct mgenx_flow_clock {           /* 64 B; one per flow */
+  uint64_t n;
+  uint64_t xa;
+  int64_t  da;
+  uint64_t xb;
+  int64_t  db;
+  int64_t  resid_sum, resid_max;
+  uint32_t ia, ib;
+};
+int mgenx_flow_clock(mgenx_ctx* ctx, const uint32_t* dev_flow_idx, const uint32_t* dev_tx_sec,
+                     const uint32_t* dev_tx_usec, const uint32_t* dev_rx_sec,
+                     const uint32_t* dev_rx_usec, uint32_t n, uint32_t n_flows, uint32_t opts,
+                     struct mgenx_flow_clock* dev_flows, int64_t* dev_resid,
+                     uint32_t* dev_rx_sec_out, uint32_t* dev_rx_usec_out, void* stream);
 
 
 /* ---- MgenAnalyticTable::FindFlow for batches (mgenAnalytic.cpp:312-328) ----

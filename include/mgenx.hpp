@@ -825,6 +825,83 @@ class MessageMatch {
   DeviceArray<uint32_t> d_s_[5], d_r_[6], cnt_, first_, rs_;
 };
 
+// ---- per-flow clock offset and skew removal ------------------------------------------------
+// mgenx_flow_clock (include/mgenx.h) over host columns: per flow the edge of the lower hull of
+// (send time, latency) over the mean send time, per record the latency above that line.  One Run
+// per log (the fit does not stream); the per-record results stay on the device until they are
+// asked for, and DevRxSec / DevRxUsec feed mgenx_flow_dist, mgenx_flow_series and
+// mgenx_flow_series_quantiles in place of the receive stamps.
+class FlowClock {
+ public:
+  typedef struct mgenx_flow_clock Flow;
+  struct Columns {
+    std::vector<uint32_t> flow_idx, tx_sec, tx_usec, rx_sec, rx_usec;
+  };
+  // opts: 0 or MGENX_CLOCK_OFFSET_ONLY
+  FlowClock(Context& ctx, uint32_t nFlows, uint32_t opts = 0)
+      : ctx_(ctx), n_flows_(nFlows), opts_(opts), flows_(nFlows) {}
+  std::vector<Flow> Run(const Columns& c) {
+    n_ = (uint32_t)c.flow_idx.size();
+    if (n_flows_ == 0) {  // nothing to fit, and nothing is written
+      n_ = 0;
+      return {};
+    }
+    const std::vector<uint32_t>* hc[5] = {&c.flow_idx, &c.tx_sec, &c.tx_usec, &c.rx_sec,
+                                          &c.rx_usec};
+    hipStream_t st = ctx_.stream();
+    for (int k = 0; k < 5; k++) {
+      if (hc[k]->size() != n_) throw Error("FlowClock: columns of unequal length");
+      d_[k].Resize(n_);
+      if (n_)
+        check_hip(hipMemcpyAsync(d_[k].data(), hc[k]->data(), (size_t)n_ * 4,
+                                 hipMemcpyHostToDevice, st), "H2D");
+    }
+    resid_.Resize(n_);
+    sec_.Resize(n_);
+    usec_.Resize(n_);
+    ctx_.Check(mgenx_flow_clock(ctx_.get(), d_[0].data(), d_[1].data(), d_[2].data(),
+                                d_[3].data(), d_[4].data(), n_, n_flows_, opts_, flows_.data(),
+                                n_ ? resid_.data() : nullptr, n_ ? sec_.data() : nullptr,
+                                n_ ? usec_.data() : nullptr, st),
+               "mgenx_flow_clock");
+    return Download(flows_, n_flows_);
+  }
+  // per record: the latency above its flow's line (INT64_MIN for a skipped record)
+  std::vector<int64_t> Residuals() { return Download(resid_, n_); }
+  // per record: the corrected receive stamp
+  std::vector<uint32_t> RxSec() { return Download(sec_, n_); }
+  std::vector<uint32_t> RxUsec() { return Download(usec_, n_); }
+  uint32_t* DevRxSec() const { return sec_.data(); }
+  uint32_t* DevRxUsec() const { return usec_.data(); }
+  Flow* DevFlows() const { return flows_.data(); }
+  // the line's slope in parts per million of the sender's clock (0 for a line through one point)
+  static double skew_ppm(const Flow& f) {
+    return f.xa == f.xb ? 0.0 : 1e6 * (double)(f.db - f.da) / (double)(f.xb - f.xa);
+  }
+  // the line's value at send time t_us, microseconds: the offset (plus the minimum path delay)
+  // as seen at that moment; by default at the line's first point
+  static double offset_us(const Flow& f) { return (double)f.da; }
+  static double offset_us(const Flow& f, uint64_t t_us) {
+    return (double)f.da + skew_ppm(f) * 1e-6 * ((double)t_us - (double)f.xa);
+  }
+
+ private:
+  template <typename T>
+  std::vector<T> Download(const DeviceArray<T>& d, size_t n) {
+    std::vector<T> out(n);
+    if (n)
+      check_hip(hipMemcpyAsync(out.data(), d.data(), n * sizeof(T), hipMemcpyDeviceToHost,
+                               ctx_.stream()), "D2H");
+    ctx_.Sync();
+    return out;
+  }
+  Context& ctx_;
+  uint32_t n_flows_, opts_, n_ = 0;
+  DeviceArray<Flow> flows_;
+  DeviceArray<int64_t> resid_;
+  DeviceArray<uint32_t> d_[5], sec_, usec_;
+};
+
 // ---- sharded stream framing: one TCP / SINK stream over the ranks of a job --------------
 // An all-gather of fixed-size u64 vectors among the ranks (host vectors in and out):
 // out[r * in.size() + k] = rank r's in[k].  The framing exchanges two kinds of message:

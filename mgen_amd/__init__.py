@@ -32,6 +32,7 @@ from ._abi import (  # noqa: F401
     ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
     PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
     MATCH_NONE, MATCH_NO_TIME, MATCH_RUN_BINS, FLOW_MATCH_DTYPE, MATCH_STATS_DTYPE,
+    CLOCK_NONE, CLOCK_OFFSET_ONLY, FLOW_CLOCK_DTYPE,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,7 +63,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_flow_series_init", "mgenx_flow_series", "mgenx_flow_series_quantiles",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
-    "mgenx_match_side", "mgenx_msg_match",
+    "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -175,6 +176,7 @@ def load(diag: bool = False):
                                     u32, P]
     L.mgenx_flow_series_quantiles.argtypes = [P, P, P, P, P, P, u32, ctypes.c_int64, u64, u32, u32,
                                               ctypes.POINTER(u32), u32, P, P]
+    L.mgenx_flow_clock.argtypes = [P, P, P, P, P, P, u32, u32, u32, P, P, P, P, P]
     L.mgenx_match_side.argtypes = [P, P, P, P, u32, u32, P, P, P]
     L.mgenx_msg_match.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P, P,
                                   P, P, P]
@@ -705,6 +707,37 @@ class Engine:
             n, int(t0_us), int(width_us), int(n_bins), n_flows, q, len(permille), _ptr(out),
             _stream(self.device)), "mgenx_flow_series_quantiles")
         return out
+
+    def flow_clock(self, n_flows, flow_idx, tx_sec, tx_usec, rx_sec, rx_usec, n=None, *,
+                   offset_only=False, resid=False, stamps=False, opts=None):
+        """Per-flow clock offset and skew (mgenx_flow_clock): the hull edge over the mean send
+        time of every flow and the latencies above it.  Returns (clock, resid, rx_sec_out,
+        rx_usec_out): a uint8 tensor of n_flows x 64 B (FLOW_CLOCK_DTYPE), an int64 tensor of n
+        residuals (None unless resid=True) and two int32 tensors of n corrected receive stamps
+        (None unless stamps=True), which mgenx_flow_dist / flow_series / flow_series_quantiles take
+        in place of rx_sec / rx_usec.  resid and stamps may also pass tensors to write into
+        (stamps: a pair).  One call takes the whole log."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        n = flow_idx.numel() if n is None else n
+        if opts is None:
+            opts = CLOCK_OFFSET_ONLY if offset_only else 0
+        clock = torch.empty(max(n_flows, 1) * FLOW_CLOCK_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        if resid is True:
+            resid = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        elif resid is False:
+            resid = None
+        if stamps is True:
+            stamps = (torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+                      torch.empty(max(n, 1), dtype=torch.int32, device=dev))
+        elif stamps is False or stamps is None:
+            stamps = (None, None)
+        self._check(self.lib.mgenx_flow_clock(
+            self.ctx, _ptr(flow_idx), _ptr(tx_sec), _ptr(tx_usec), _ptr(rx_sec), _ptr(rx_usec), n,
+            n_flows, opts, _ptr(clock), _ptr(resid), _ptr(stamps[0]), _ptr(stamps[1]),
+            _stream(self.device)), "mgenx_flow_clock")
+        return clock[:n_flows * FLOW_CLOCK_DTYPE.itemsize], resid, stamps[0], stamps[1]
 
     def match_side(self, parsed, n, want_event):
         """A parsed log (log_parse_text) made ready for flow_lookup as one side of msg_match
@@ -1274,13 +1307,73 @@ def flow_dist_bin_lo(b: int) -> int:
     return int(load().mgenx_flow_dist_bin_lo(int(b)))
 
 
+def _clock_opts(clock):
+    """The `clock` keyword of the analysis helpers: None (raw latencies), "fit" (offset and skew
+    removed per flow, mgenx_flow_clock) or "offset" (MGENX_CLOCK_OFFSET_ONLY) -> None or opts."""
+    if clock is None:
+        return None
+    if clock == "fit":
+        return 0
+    if clock == "offset":
+        return CLOCK_OFFSET_ONLY
+    raise ValueError('clock must be None, "fit" or "offset"')
+
+
+def _clock_rx(eng, clock_opts, nf, flow_idx, p, n):
+    """The receive stamps an analysis reads: the parsed ones, or with a clock option the stamps
+    mgenx_flow_clock corrects (the latency above each flow's fitted line, on the sender's clock)."""
+    if clock_opts is None:
+        return p["rx_sec"], p["rx_usec"]
+    _, _, rs, ru = eng.flow_clock(nf, flow_idx, p["tx_sec"], p["tx_usec"], p["rx_sec"],
+                                  p["rx_usec"], n=n, opts=clock_opts, stamps=True)
+    return rs, ru
+
+
+def analyze_text_log_clock(log_bytes, offset_only=False, day_base=0, device=0) -> tuple:
+    """Per-flow clock offset and skew of an MGEN text log, on the GPU: line index -> parse ->
+    FindFlow -> mgenx_flow_clock.  Returns (keys, clock, n_lines, n_malformed): numpy arrays of
+    REPORT_KEY_DTYPE and FLOW_CLOCK_DTYPE, flows in analyze_text_log's order."""
+    import torch
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
+        line_off, n = eng.text_index(text)
+        empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_CLOCK_DTYPE))
+        if n == 0:
+            return empty + (0, 0)
+        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+        n_bad = int((p["status"] != PARSE_OK).sum().item())
+        table = eng.flow_table(max(n, 16))
+        flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
+        nf = int(n_flows.item())
+        if nf == 0:
+            return empty + (n, n_bad)
+        clock, _, _, _ = eng.flow_clock(nf, flow_idx, p["tx_sec"], p["tx_usec"], p["rx_sec"],
+                                        p["rx_usec"], n=n, offset_only=offset_only)
+        recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
+        proto = int(p["protocol"][recv][0].item())
+        keys = eng.flow_keys(table, nf, protocol=proto)
+        torch.cuda.synchronize(device)
+        return (keys.cpu().numpy().view(REPORT_KEY_DTYPE)[:nf].copy(),
+                clock.cpu().numpy().view(FLOW_CLOCK_DTYPE)[:nf].copy(), n, n_bad)
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
+        eng.close()
+
+
 def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
-                          device=0) -> tuple:
+                          device=0, clock=None) -> tuple:
     """Per-flow delivery statistics of an MGEN text log, on the GPU: line index -> parse ->
     FindFlow -> mgenx_flow_dist -> quantiles.  Returns (keys, dist, quantiles, hist, n_lines,
     n_malformed): numpy arrays of REPORT_KEY_DTYPE and FLOW_DIST_DTYPE, int64 [n_flows,
-    len(permille)] and uint64 [n_flows, FLOW_DIST_BINS], flows in analyze_text_log's order."""
+    len(permille)] and uint64 [n_flows, FLOW_DIST_BINS], flows in analyze_text_log's order.
+    clock="fit" or "offset" runs mgenx_flow_clock first and feeds the corrected receive stamps
+    onward: every latency is then the delay above the flow's fitted line."""
     import torch
+    clock_opts = _clock_opts(clock)
     eng = Engine(device)
     table = None
     try:
@@ -1298,9 +1391,10 @@ def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
         nf = int(n_flows.item())
         if nf == 0:
             return empty + (n, n_bad)
+        rx_sec, rx_usec = _clock_rx(eng, clock_opts, nf, flow_idx, p, n)
         dist, hist = eng.flow_dist_init(nf)
         eng.flow_dist(dist, hist, nf, flow_idx, p["seq_num"], p["tx_sec"], p["tx_usec"],
-                      p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+                      p["msg_len"], rx_sec, rx_usec, n=n)
         quant = eng.flow_dist_quantiles(dist, hist, nf, permille)
         recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
         proto = int(p["protocol"][recv][0].item())
@@ -1316,7 +1410,7 @@ def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
 
 
 def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_base=0,
-                            device=0, permille=None) -> tuple:
+                            device=0, permille=None, clock=None) -> tuple:
     """Per-flow time series of an MGEN text log, on the GPU: line index -> parse -> FindFlow ->
     mgenx_flow_series.  Returns (keys, state, bins, t0_us, n_lines, n_malformed): numpy arrays
     of REPORT_KEY_DTYPE, FLOW_SERIES_STATE_DTYPE and FLOW_SERIES_BIN_DTYPE [n_flows, n_bins],
@@ -1324,8 +1418,11 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
     counted records and n_bins just enough to hold the highest (mgenx_flow_span).  With
     `permille` (values in 1..1000) the same parse also feeds mgenx_flow_series_quantiles and the
     tuple gains a seventh element: the exact latency percentiles, int64 [n_flows, n_bins,
-    len(permille)]."""
+    len(permille)].  clock="fit" or "offset" runs mgenx_flow_clock first and feeds the corrected
+    receive stamps onward (the time axis is then the sender's clock, every latency the delay above
+    the flow's fitted line)."""
     import torch
+    clock_opts = _clock_opts(clock)
     width_us = int(width_us)
     if permille is not None:
         permille = tuple(int(q) for q in permille)
@@ -1354,8 +1451,9 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
         nf = int(n_flows.item())
         if nf == 0:
             return empty(n, n_bad)
+        rx_sec, rx_usec = _clock_rx(eng, clock_opts, nf, flow_idx, p, n)
         if t0_us is None or n_bins is None:
-            _, lo, hi = eng.flow_span(flow_idx, p["rx_sec"], p["rx_usec"], n, nf)
+            _, lo, hi = eng.flow_span(flow_idx, rx_sec, rx_usec, n, nf)
             if t0_us is None:
                 t0_us = lo
             if n_bins is None:
@@ -1363,12 +1461,11 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
         t0_us, n_bins = int(t0_us), int(n_bins)
         state, bins = eng.flow_series_init(nf, n_bins)
         eng.flow_series(state, bins, nf, n_bins, t0_us, width_us, flow_idx, p["seq_num"],
-                        p["tx_sec"], p["tx_usec"], p["msg_len"], p["rx_sec"], p["rx_usec"], n=n)
+                        p["tx_sec"], p["tx_usec"], p["msg_len"], rx_sec, rx_usec, n=n)
         quant = None
         if permille is not None:
             quant = eng.flow_series_quantiles(nf, n_bins, t0_us, width_us, permille, flow_idx,
-                                              p["tx_sec"], p["tx_usec"], p["rx_sec"],
-                                              p["rx_usec"], n=n)
+                                              p["tx_sec"], p["tx_usec"], rx_sec, rx_usec, n=n)
         recv = (p["event"] == EVENT_RECV) & (p["status"] == PARSE_OK)
         proto = int(p["protocol"][recv][0].item())
         keys = eng.flow_keys(table, nf, protocol=proto)

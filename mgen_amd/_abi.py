@@ -173,6 +173,14 @@ MATCH_STATS_DTYPE = np.dtype([
     ("send_dup", "<u8")])
 assert FLOW_MATCH_DTYPE.itemsize == 256 and MATCH_STATS_DTYPE.itemsize == 32
 
+# ---- per-flow clock offset and skew (mgenx_flow_clock, include/mgenx.h) ----
+CLOCK_NONE = 0xFFFFFFFF     # MGENX_CLOCK_NONE
+CLOCK_OFFSET_ONLY = 0x1     # MGENX_CLOCK_OFFSET_ONLY
+FLOW_CLOCK_DTYPE = np.dtype([
+    ("n", "<u8"), ("xa", "<u8"), ("da", "<i8"), ("xb", "<u8"), ("db", "<i8"),
+    ("resid_sum", "<i8"), ("resid_max", "<i8"), ("ia", "<u4"), ("ib", "<u4")])
+assert FLOW_CLOCK_DTYPE.itemsize == 64
+
 
 # ---- pcap2mgen / text interleave (include/mgenx.h) ----
 class PcapInfo(ctypes.Structure):      # mgenx_pcap_info

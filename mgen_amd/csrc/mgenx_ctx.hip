@@ -192,6 +192,7 @@ int mgenx_ctx_destroy(mgenx_ctx* c) {
   c->flowdist_ws.release();
   c->flowseries_ws.release();
   c->flowquant_ws.release();
+  c->flowclock_ws.release();
   c->match_ws.release();
   if (c->log_ws) mgenx::log_ws_free(c->log_ws);
   c->tcp_ws.release();

@@ -110,6 +110,7 @@ struct mgenx_ctx {
   mgenx::DevBuf flowdist_ws;      // flow-dist workspace (mgenx_flowdist.hip)
   mgenx::DevBuf flowseries_ws;    // flow-series workspace (mgenx_flowseries.hip)
   mgenx::DevBuf flowquant_ws;     // windowed-percentile workspace (mgenx_flowquant.hip)
+  mgenx::DevBuf flowclock_ws;     // clock offset / skew workspace (mgenx_flowclock.hip)
   mgenx::DevBuf match_ws;         // msg-match workspace (mgenx_match.hip)
   mgenx::DevBuf tcp_ws;           // TCP transmit workspace (mgenx_pack_tcp)
   uint64_t* tcp_host = nullptr;   // host-mapped words: the plan's verdict (16 bytes)
@@ -184,7 +185,8 @@ int flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n, uint32_t n_fl
                   const uint32_t** keys, const uint32_t** order, const uint32_t** bnd,
                   hipStream_t stream, char* err, size_t errn);
 
-// ---- mgenx_flowdist.hip, mgenx_flowseries.hip, mgenx_flowquant.hip, mgenx_match.hip ----
+// ---- mgenx_flowdist.hip, mgenx_flowseries.hip, mgenx_flowquant.hip, mgenx_flowclock.hip,
+// ---- mgenx_match.hip ----
 int flow_dist_init_run(struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
                        hipStream_t stream);
 // The passes mgenx_flow_dist and mgenx_flow_series share: the stable sort by flow (keys / order /
@@ -218,6 +220,13 @@ int flow_quant_run(DevBuf& ws, int cu_count, const uint32_t* flow_idx, const uin
                    int64_t t0, uint64_t width, uint32_t n_bins, uint32_t n_flows,
                    const uint32_t* permille, uint32_t n_q, int64_t* out, hipStream_t stream,
                    char* err, size_t errn);
+// mgenx_flowclock.hip: n_flows >= 1; n, n_flows < 2^31; resid optional, sec_out / usec_out both
+// or neither.  cu_count sizes the grids that walk the flows.
+int flow_clock_run(DevBuf& ws, int cu_count, const uint32_t* flow_idx, const uint32_t* txs,
+                   const uint32_t* txu, const uint32_t* rxs, const uint32_t* rxu, uint32_t n,
+                   uint32_t n_flows, uint32_t opts, struct mgenx_flow_clock* flows, int64_t* resid,
+                   uint32_t* sec_out, uint32_t* usec_out, hipStream_t stream, char* err,
+                   size_t errn);
 int match_side_run(const uint8_t* event, const uint8_t* status, const mgenx_addr* src, uint32_t n,
                    uint32_t want_event, mgenx_addr* src_out, uint8_t* err_out, hipStream_t stream);
 int msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_seq, const uint32_t* s_sec,

@@ -1,6 +1,6 @@
 """Per-flow time series of an MGEN receiver log as a table to plot.
 
-    python -m mgen_amd.series [-q 500,950,990] <log> <width_sec> [outfile]
+    python -m mgen_amd.series [-q 500,950,990] [-c fit|offset] <log> <width_sec> [outfile]
 
 reads a text log, reduces it on the GPU (analyze_text_log_series: mgenx_flow_series, one time
 axis for all flows) and writes, per flow, a comment line and one row per non-empty window:
@@ -17,6 +17,10 @@ back later = late, mean latency = lat_sum / n, mean jitter = jitter_sum / n.
 positional arguments, and appends one column per value, lat_p500 lat_p950 lat_p990 for the list
 above: the window's exact latency percentiles (mgenx_flow_series_quantiles, the rank rule of
 mgenx_flow_dist_quantiles).  Rows exist only for non-empty windows, so every value is a latency.
+
+-c fit (or -c offset), likewise before or after the positional arguments, removes each flow's
+clock offset and skew (or its offset alone) first (mgenx_flow_clock): the time axis is then the
+sender's clock and every latency column the delay above the flow's fitted line.
 """
 from __future__ import annotations
 
@@ -57,6 +61,13 @@ def parse_permille(text) -> tuple:
     return tuple(out)
 
 
+def parse_clock(text) -> str:
+    """The argument of -c: "fit" or "offset".  ValueError for anything else."""
+    if text not in ("fit", "offset"):
+        raise ValueError("-c takes fit or offset, not %r" % (text,))
+    return text
+
+
 def format_series(keys, bins, t0_us, width_us, quant=None, permille=()) -> str:
     """The table described above.  keys: REPORT_KEY_DTYPE [n_flows]; bins: FLOW_SERIES_BIN_DTYPE
     [n_flows, n_bins]; quant: None, or int64 [n_flows, n_bins, len(permille)] for the columns
@@ -87,8 +98,21 @@ def format_series(keys, bins, t0_us, width_us, quant=None, permille=()) -> str:
 
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    usage = "usage: python -m mgen_amd.series [-q 500,950,990] <log> <width_sec> [outfile]\n"
+    usage = ("usage: python -m mgen_amd.series [-q 500,950,990] [-c fit|offset] <log> <width_sec> "
+             "[outfile]\n")
     permille = None
+    clock = None
+    if "-c" in argv:
+        at = argv.index("-c")
+        if at + 1 >= len(argv) or "-c" in argv[at + 2:]:
+            sys.stderr.write(usage)
+            return 2
+        try:
+            clock = parse_clock(argv[at + 1])
+        except ValueError as e:
+            sys.stderr.write("series: %s\n" % e)
+            return 2
+        del argv[at:at + 2]
     if "-q" in argv:
         at = argv.index("-q")
         if at + 1 >= len(argv) or "-q" in argv[at + 2:]:
@@ -111,12 +135,13 @@ def main(argv=None) -> int:
     from . import analyze_text_log_series
     with open(argv[0], "rb") as fh:
         log = fh.read()
+    kw = {} if clock is None else {"clock": clock}
     if permille is None:
-        keys, _state, bins, t0_us, n_lines, n_bad = analyze_text_log_series(log, width_us)
+        keys, _state, bins, t0_us, n_lines, n_bad = analyze_text_log_series(log, width_us, **kw)
         text = format_series(keys, bins, t0_us, width_us)
     else:
         keys, _state, bins, t0_us, n_lines, n_bad, quant = analyze_text_log_series(
-            log, width_us, permille=permille)
+            log, width_us, permille=permille, **kw)
         text = format_series(keys, bins, t0_us, width_us, quant, permille)
     if len(argv) == 3:
         with open(argv[2], "w") as fh:
