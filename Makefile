@@ -28,7 +28,8 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/shard_scan tools/pcap2mgen tests/cpp/logparse_host \
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
      tests/cpp/flow_series_host tests/cpp/msg_match_host tests/cpp/flow_quant_host \
-     tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host
+     tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host \
+     tests/cpp/match_timeline_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -131,6 +132,11 @@ tests/cpp/flow_clock_host: tests/cpp/flow_clock_host.cpp include/mgenx.hpp inclu
 
 # mgenx::MessageMatch over a sender's and a receiver's records against a serial loop in the program
 tests/cpp/msg_match_host: tests/cpp/msg_match_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
+	$(HOSTCXX) $< -o $@ $(HOSTLD)
+
+# mgenx::MessageMatch::RunTimeline (the series per send-time window, the loss runs, the owner
+# column) against a serial loop in the program
+tests/cpp/match_timeline_host: tests/cpp/match_timeline_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
 	$(HOSTCXX) $< -o $@ $(HOSTLD)
 
 # mgenx::Pcap2Mgen with PcapOptions::tcp over a capture file (tests/test_gpu_pcap_tcp_cpp.py)

@@ -1538,6 +1538,82 @@ int mgenx_msg_match(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                     struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
                     void* stream);
 
+/* ---- the same join on the sender's time axis: loss per send-time window, and the loss runs ----
+ * mgenx_msg_match_ex is mgenx_msg_match (the same arguments, the same outputs, the same bytes)
+ * plus a timeline of up to three optional parts, all in mgenx_msg_match's terms: counted record,
+ * identity, owner, send duplicate, delivered.  With tl == NULL, or a timeline with all three
+ * parts off, the call is mgenx_msg_match: the same launches and the same bytes.
+ *
+ * Owner column (dev_send_owner, ns elements; null: not wanted): dev_send_owner[i] = the lowest
+ * index among the counted send records with record i's identity (i itself for an owner), or
+ * MGENX_MATCH_NONE for a skipped record.
+ *
+ * Send stamp of record i: t = t_sec[i] * 10^6 + t_usec[i], the u32 values widened to signed 64
+ * bit first; a t_usec >= 10^6 is taken as it is.  The latency of a delivered owner is
+ * mgenx_msg_match's: the rx stamp of recv record send_first_rx minus t.
+ *
+ * Series (n_bins > 0): dev_bins[f * n_bins + b] is the window [t0_us + b width_us,
+ * t0_us + (b + 1) width_us) of send time of flow f.  For every owner i of flow f,
+ * b = floor((t - t0_us) / width_us), a signed floor; outside [0, n_bins) the owner adds 1 to
+ * dev_outside[f] and touches no bin; else the cell takes sent += 1 and sent_bytes += len, and
+ * when the owner is delivered also delivered += 1, delivered_bytes += len,
+ * rx_dup += send_rx_count - 1, and lat_sum / lat_min / lat_max from the latency.  Send duplicates
+ * and skipped records count nowhere: under MGENX_MATCH_NO_TIME a duplicate may carry another
+ * stamp, and only the owner's stamp places the message.  Every cell and every dev_outside
+ * element is written on every call (no init call); an empty cell holds zeros, INT64_MAX and
+ * INT64_MIN.  Over a flow with outside == 0 the bins sum to mgenx_flow_match's sent, sent_bytes,
+ * delivered, delivered_bytes, rx_dup and (wrapping) lat_sum, and the extreme of the bins' minima
+ * and maxima is the flow's lat_min / lat_max.
+ *
+ * Run list (dev_n_runs non-null): the runs are mgenx_msg_match's, maximal runs of consecutive
+ * undelivered owners of a flow in send-log order; send duplicates are transparent, head and tail
+ * runs count.  One mgenx_loss_run per run with length >= max(min_run, 1), ordered by flow_idx,
+ * then by first_send.  first_send and last_send are the run's first and last undelivered owner
+ * (never a send duplicate next to it), t_first_us / t_last_us their send stamps.
+ * MGENX_RUN_HEAD: no delivered owner of the flow before the run; MGENX_RUN_TAIL: none after it (a
+ * flow never delivered has one run with both).  dev_n_runs[0] = the number of such runs, always
+ * written; dev_runs[0 .. count) is written only when count <= run_cap, else not one byte of
+ * dev_runs changes: call once with run_cap 0, size the list, call again (the two-pass convention
+ * of mgenx_log_recv_text).  With min_run <= 1 the count is the sum of loss_runs over the flows.
+ *
+ * ns == 0, nr == 0 and n_flows == 0 are legal: empty cells, zero counts.  The timeline adds 8
+ * bytes per send record and 20 per 1024 of them to the workspace.  MGENX_EINVAL, before any HIP
+ * call, beside mgenx_msg_match's: with n_bins > 0 a width_us of 0, a t0_us outside
+ * [-2^62, 2^62], n_flows * n_bins >= 2^31, or a null dev_bins or dev_outside while n_flows > 0;
+ * dev_n_runs given with a null dev_runs while run_cap > 0.  Integer arithmetic only; every
+ * output byte is a function of the inputs alone. */
+#define MGENX_RUN_HEAD 0x1   /* no delivered owner of the flow before the run */
+#define MGENX_RUN_TAIL 0x2   /* none after it (a flow never delivered: both) */
+struct mgenx_match_bin {     /* 64 B; one per (flow, window of send time) */
+  uint64_t sent, sent_bytes, delivered, delivered_bytes, rx_dup;
+  int64_t  lat_sum, lat_min, lat_max;   /* INT64_MAX / INT64_MIN while delivered == 0; the sum wraps */
+};
+struct mgenx_loss_run {      /* 40 B */
+  uint32_t flow_idx, length;            /* undelivered owners in the run */
+  uint32_t first_send, last_send;       /* send-record indices of its first and last undelivered owner */
+  uint32_t flags, rsv;                  /* MGENX_RUN_*; 0 */
+  int64_t  t_first_us, t_last_us;       /* the send stamps of first_send / last_send */
+};
+typedef struct {             /* HOST struct; each of the three parts is optional */
+  int64_t  t0_us; uint64_t width_us; uint32_t n_bins;   /* n_bins == 0: no series */
+  uint32_t min_run;                                      /* 0 is taken as 1 */
+  struct mgenx_match_bin* dev_bins;    /* [n_flows * n_bins], row f = flow f */
+  uint64_t* dev_outside;               /* [n_flows] */
+  struct mgenx_loss_run* dev_runs; uint64_t run_cap;
+  uint64_t* dev_n_runs;                /* null: no run list */
+  uint32_t* dev_send_owner;            /* [ns], null: not wanted */
+} mgenx_match_timeline;
+int mgenx_msg_match_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                       const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                       const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len, uint32_t ns,
+                       const uint32_t* dev_recv_flow_idx, const uint32_t* dev_recv_seq,
+                       const uint32_t* dev_recv_tx_sec, const uint32_t* dev_recv_tx_usec,
+                       const uint32_t* dev_recv_rx_sec, const uint32_t* dev_recv_rx_usec,
+                       uint32_t nr, uint32_t n_flows, uint32_t opts, uint32_t* dev_send_rx_count,
+                       uint32_t* dev_send_first_rx, uint32_t* dev_recv_send,
+                       struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
+                       const mgenx_match_timeline* tl, void* stream);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ----
  * One communicator per rank (one process per GPU): rank 0 calls mgenx_comm_unique_id and
  * hands the MGENX_COMM_ID_BYTES bytes to every rank (any out-of-band channel), then every

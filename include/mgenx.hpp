@@ -793,6 +793,59 @@ class MessageMatch {
                "mgenx_msg_match");
     ctx_.Sync();  // the host vectors are the caller's again
   }
+  // Run plus the timeline of mgenx_msg_match_ex: the series per send-time window (nBins windows
+  // of width_us from t0_us; nBins == 0: none), the runs of at least minRun lost messages, and the
+  // owner column.  The run list is sized by a first call and the call is repeated once.
+  typedef struct mgenx_match_bin Bin;
+  typedef struct mgenx_loss_run LossRun;
+  void RunTimeline(const SendColumns& s, const RecvColumns& r, int64_t t0_us, uint64_t width_us,
+                   uint32_t nBins, uint32_t minRun = 1) {
+    ns_ = (uint32_t)s.flow_idx.size();
+    nr_ = (uint32_t)r.flow_idx.size();
+    const std::vector<uint32_t>* sc[5] = {&s.flow_idx, &s.seq, &s.t_sec, &s.t_usec, &s.len};
+    const std::vector<uint32_t>* rc[6] = {&r.flow_idx, &r.seq,    &r.tx_sec,
+                                          &r.tx_usec,  &r.rx_sec, &r.rx_usec};
+    hipStream_t st = ctx_.stream();
+    for (int k = 0; k < 5; k++) Upload(d_s_[k], *sc[k], ns_, st);
+    for (int k = 0; k < 6; k++) Upload(d_r_[k], *rc[k], nr_, st);
+    cnt_.Resize(ns_);
+    first_.Resize(ns_);
+    rs_.Resize(nr_);
+    own_.Resize(ns_);
+    n_bins_ = nBins;
+    bins_.Resize((size_t)n_flows_ * nBins);
+    outside_.Resize(nBins ? n_flows_ : 0);
+    n_runs_dev_.Resize(1);
+    mgenx_match_timeline tl = {};
+    tl.t0_us = t0_us;
+    tl.width_us = width_us;
+    tl.n_bins = nBins;
+    tl.min_run = minRun;
+    tl.dev_bins = bins_.data();
+    tl.dev_outside = outside_.data();
+    tl.dev_n_runs = n_runs_dev_.data();
+    tl.dev_send_owner = own_.data();
+    n_runs_ = 0;
+    for (int pass = 0; pass < 2; pass++) {
+      tl.dev_runs = runs_.data();
+      tl.run_cap = pass ? n_runs_ : 0;
+      ctx_.Check(mgenx_msg_match_ex(ctx_.get(), d_s_[0].data(), d_s_[1].data(), d_s_[2].data(),
+                                    d_s_[3].data(), d_s_[4].data(), ns_, d_r_[0].data(),
+                                    d_r_[1].data(), d_r_[2].data(), d_r_[3].data(),
+                                    d_r_[4].data(), d_r_[5].data(), nr_, n_flows_, opts_,
+                                    cnt_.data(), first_.data(), rs_.data(), flows_.data(),
+                                    stats_.data(), &tl, st),
+                 "mgenx_msg_match_ex");
+      n_runs_ = Download(n_runs_dev_, 1)[0];  // (synchronises)
+      if (pass || n_runs_ == 0) break;
+      runs_.Resize(n_runs_);
+    }
+  }
+  std::vector<Bin> Bins() { return Download(bins_, (size_t)n_flows_ * n_bins_); }  // row f = flow f
+  std::vector<uint64_t> Outside() { return Download(outside_, n_bins_ ? n_flows_ : 0); }
+  std::vector<LossRun> Runs() { return Download(runs_, n_runs_); }
+  // per send record: its identity's owner (itself for an owner), MGENX_MATCH_NONE when skipped
+  std::vector<uint32_t> SendOwner() { return Download(own_, ns_); }
   std::vector<Flow> Flows() { return Download(flows_, n_flows_); }
   Stats GetStats() { return Download(stats_, 1)[0]; }
   // per send record: the recv records with its identity (0 for a duplicate) and the first of them
@@ -823,6 +876,12 @@ class MessageMatch {
   DeviceArray<Flow> flows_;
   DeviceArray<Stats> stats_;
   DeviceArray<uint32_t> d_s_[5], d_r_[6], cnt_, first_, rs_;
+  uint32_t n_bins_ = 0;
+  uint64_t n_runs_ = 0;
+  DeviceArray<Bin> bins_;
+  DeviceArray<LossRun> runs_;
+  DeviceArray<uint64_t> outside_, n_runs_dev_;
+  DeviceArray<uint32_t> own_;
 };
 
 // ---- per-flow clock offset and skew removal ------------------------------------------------

@@ -32,6 +32,7 @@ from ._abi import (  # noqa: F401
     ENOSPC, PCAP_FRAGMENT, DEFRAG_MAX_FRAGS, DefragStats,
     PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
     MATCH_NONE, MATCH_NO_TIME, MATCH_RUN_BINS, FLOW_MATCH_DTYPE, MATCH_STATS_DTYPE,
+    RUN_HEAD, RUN_TAIL, MATCH_BIN_DTYPE, LOSS_RUN_DTYPE, MatchTimeline,
     CLOCK_NONE, CLOCK_OFFSET_ONLY, FLOW_CLOCK_DTYPE,
 )
 
@@ -63,7 +64,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_flow_series_init", "mgenx_flow_series", "mgenx_flow_series_quantiles",
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
-    "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock",
+    "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock", "mgenx_msg_match_ex",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -180,6 +181,8 @@ def load(diag: bool = False):
     L.mgenx_match_side.argtypes = [P, P, P, P, u32, u32, P, P, P]
     L.mgenx_msg_match.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P, P,
                                   P, P, P]
+    L.mgenx_msg_match_ex.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P,
+                                     P, P, P, ctypes.POINTER(MatchTimeline), P]
     L.mgenx_flow_dist_bin.argtypes = [u64]
     L.mgenx_flow_dist_bin.restype = u32
     L.mgenx_flow_dist_bin_lo.argtypes = [u32]
@@ -781,6 +784,53 @@ class Engine:
             _ptr(flows), _ptr(stats), _stream(self.device)), "mgenx_msg_match")
         return (cnt[:ns], first[:ns], rs[:nr], flows[:n_flows * FLOW_MATCH_DTYPE.itemsize],
                 stats)
+
+    def msg_match_timeline(self, n_flows, send, recv, t0_us, width_us, n_bins, *, min_run=1,
+                           opts=0, ns=None, nr=None):
+        """msg_match plus the timeline of mgenx_msg_match_ex on the sender's time axis.  Returns
+        msg_match's tuple followed by bins (uint8, n_flows x n_bins x 64 B: MATCH_BIN_DTYPE),
+        outside (int64, n_flows), runs (uint8, n_runs x 40 B: LOSS_RUN_DTYPE, the runs of at
+        least min_run lost messages by flow and first send index) and owner (int32, ns).  The
+        run list is sized by a first call and the call is repeated once (one read-back)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        ns = send["flow_idx"].numel() if ns is None else ns
+        nr = recv["flow_idx"].numel() if nr is None else nr
+        cnt = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        owner = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        rs = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
+        flows = torch.empty(max(n_flows, 1) * FLOW_MATCH_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        stats = torch.empty(MATCH_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        cells = n_flows * n_bins
+        bins = torch.empty(max(cells, 1) * MATCH_BIN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        outside = torch.zeros(max(n_flows, 1), dtype=torch.int64, device=dev)
+        n_runs = torch.zeros(1, dtype=torch.int64, device=dev)
+        runs = torch.empty(0, dtype=torch.uint8, device=dev)
+        tl = MatchTimeline(t0_us=t0_us, width_us=width_us, n_bins=n_bins, min_run=min_run,
+                           dev_bins=bins.data_ptr(), dev_outside=outside.data_ptr(),
+                           dev_runs=None, run_cap=0, dev_n_runs=n_runs.data_ptr(),
+                           dev_send_owner=owner.data_ptr())
+        count = 0
+        for again in (False, True):
+            self._check(self.lib.mgenx_msg_match_ex(
+                self.ctx, _ptr(send["flow_idx"]), _ptr(send["seq"]), _ptr(send["t_sec"]),
+                _ptr(send["t_usec"]), _ptr(send["len"]), ns, _ptr(recv["flow_idx"]),
+                _ptr(recv["seq"]), _ptr(recv["tx_sec"]), _ptr(recv["tx_usec"]),
+                _ptr(recv["rx_sec"]), _ptr(recv["rx_usec"]), nr, n_flows, opts, _ptr(cnt),
+                _ptr(first), _ptr(rs), _ptr(flows), _ptr(stats), ctypes.byref(tl),
+                _stream(self.device)), "mgenx_msg_match_ex")
+            if again:
+                break
+            count = int(n_runs.item())
+            if count == 0:
+                break
+            runs = torch.empty(count * LOSS_RUN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            tl.dev_runs, tl.run_cap = runs.data_ptr(), count
+        return (cnt[:ns], first[:ns], rs[:nr], flows[:n_flows * FLOW_MATCH_DTYPE.itemsize],
+                stats, bins[:cells * MATCH_BIN_DTYPE.itemsize], outside[:n_flows], runs,
+                owner[:ns])
 
     def flow_keys(self, table, n_flows, protocol=1, keys=None):
         """The report_msg key of every flow index < n_flows (mgenx_flow_keys): a uint8
@@ -1492,6 +1542,24 @@ def match_text_logs(send_log_bytes, recv_log_bytes, no_time=False, day_base=0, d
     receiver's.  Flows are numbered by their first SEND line; the receiver-only flows follow
     from index n_send_flows.  The keys' source addresses are cleared (a SEND line has the port
     only) and their protocol is that of the first OK SEND line."""
+    return _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, None)
+
+
+def match_text_logs_timeline(send_log, recv_log, width_us, t0_us=None, n_bins=None, min_run=1,
+                             no_time=False, day_base=0, device=0) -> tuple:
+    """match_text_logs on the sender's time axis (mgenx_msg_match_ex): the exact loss per window
+    of send time and the loss runs.  Returns (keys, flows, stats, bins, outside, runs, t0_us,
+    n_send_flows): keys, flows and stats as match_text_logs gives them, bins MATCH_BIN_DTYPE
+    [n_flows, n_bins] (window b starts at t0_us + b * width_us), outside uint64 [n_flows] (the
+    messages sent outside the windows), runs LOSS_RUN_DTYPE (the runs of at least min_run lost
+    messages, by flow and first send index; first_send / last_send are 0-based lines of the
+    sender's log).  By default t0_us is the lowest SEND stamp of the sender's log and n_bins just
+    enough for the highest (mgenx_flow_span over the sender's columns)."""
+    tl = dict(width_us=int(width_us), t0_us=t0_us, n_bins=n_bins, min_run=int(min_run))
+    return _match_text_logs(send_log, recv_log, no_time, day_base, device, tl)
+
+
+def _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, tl) -> tuple:
     import torch
     eng = Engine(device)
     table = None
@@ -1541,8 +1609,25 @@ def match_text_logs(send_log_bytes, recv_log_bytes, no_time=False, day_base=0, d
         if nr:
             recv.update(seq=r["seq_num"], tx_sec=r["tx_sec"], tx_usec=r["tx_usec"],
                         rx_sec=r["rx_sec"], rx_usec=r["rx_usec"])
-        cnt, first, rs, flows, stats = eng.msg_match(
-            nf, send, recv, opts=MATCH_NO_TIME if no_time else 0, ns=ns, nr=nr)
+        opts = MATCH_NO_TIME if no_time else 0
+        if tl is None:
+            cnt, first, rs, flows, stats = eng.msg_match(nf, send, recv, opts=opts, ns=ns, nr=nr)
+        else:
+            t0_us, n_bins = tl["t0_us"], tl["n_bins"]
+            if t0_us is None or n_bins is None:
+                lo, hi = 2**64 - 1, 0
+                if ns and nf:
+                    _, lo, hi = eng.flow_span(s_idx, s["rx_sec"], s["rx_usec"], ns, nf)
+                if lo > hi:                  # no SEND line counts
+                    lo = hi = 0
+                if t0_us is None:
+                    t0_us = lo
+                if n_bins is None:
+                    n_bins = max((hi - int(t0_us)) // tl["width_us"] + 1, 1)
+            t0_us, n_bins = int(t0_us), int(n_bins)
+            cnt, first, rs, flows, stats, bins, outside, runs, _owner = eng.msg_match_timeline(
+                nf, send, recv, t0_us, tl["width_us"], n_bins, min_run=tl["min_run"], opts=opts,
+                ns=ns, nr=nr)
         keys = np.zeros(0, REPORT_KEY_DTYPE)
         if nf:
             proto = 1
@@ -1556,6 +1641,12 @@ def match_text_logs(send_log_bytes, recv_log_bytes, no_time=False, day_base=0, d
                 REPORT_KEY_DTYPE)[:nf].copy()
         torch.cuda.synchronize(device)
         u32 = lambda t: t.cpu().numpy().view(np.uint32).copy()  # noqa: E731
+        if tl is not None:
+            return (keys, flows.cpu().numpy().view(FLOW_MATCH_DTYPE).copy(),
+                    stats.cpu().numpy().view(MATCH_STATS_DTYPE)[0].copy(),
+                    bins.cpu().numpy().view(MATCH_BIN_DTYPE).reshape(nf, n_bins).copy(),
+                    outside.cpu().numpy().view(np.uint64).copy(),
+                    runs.cpu().numpy().view(LOSS_RUN_DTYPE).copy(), t0_us, n_send)
         return (keys, flows.cpu().numpy().view(FLOW_MATCH_DTYPE).copy(),
                 stats.cpu().numpy().view(MATCH_STATS_DTYPE)[0].copy(), u32(cnt), u32(first),
                 u32(rs), n_send)

@@ -172,6 +172,24 @@ MATCH_STATS_DTYPE = np.dtype([
     ("send_skipped", "<u8"), ("recv_skipped", "<u8"), ("recv_unmatched", "<u8"),
     ("send_dup", "<u8")])
 assert FLOW_MATCH_DTYPE.itemsize == 256 and MATCH_STATS_DTYPE.itemsize == 32
+# the timeline of mgenx_msg_match_ex: struct mgenx_match_bin, struct mgenx_loss_run
+RUN_HEAD = 0x1            # MGENX_RUN_HEAD
+RUN_TAIL = 0x2            # MGENX_RUN_TAIL
+MATCH_BIN_DTYPE = np.dtype([
+    ("sent", "<u8"), ("sent_bytes", "<u8"), ("delivered", "<u8"), ("delivered_bytes", "<u8"),
+    ("rx_dup", "<u8"), ("lat_sum", "<i8"), ("lat_min", "<i8"), ("lat_max", "<i8")])
+LOSS_RUN_DTYPE = np.dtype([
+    ("flow_idx", "<u4"), ("length", "<u4"), ("first_send", "<u4"), ("last_send", "<u4"),
+    ("flags", "<u4"), ("rsv", "<u4"), ("t_first_us", "<i8"), ("t_last_us", "<i8")])
+assert MATCH_BIN_DTYPE.itemsize == 64 and LOSS_RUN_DTYPE.itemsize == 40
+
+
+class MatchTimeline(ctypes.Structure):   # mgenx_match_timeline (a host struct)
+    _fields_ = [("t0_us", ctypes.c_int64), ("width_us", ctypes.c_uint64),
+                ("n_bins", ctypes.c_uint32), ("min_run", ctypes.c_uint32),
+                ("dev_bins", ctypes.c_void_p), ("dev_outside", ctypes.c_void_p),
+                ("dev_runs", ctypes.c_void_p), ("run_cap", ctypes.c_uint64),
+                ("dev_n_runs", ctypes.c_void_p), ("dev_send_owner", ctypes.c_void_p)]
 
 # ---- per-flow clock offset and skew (mgenx_flow_clock, include/mgenx.h) ----
 CLOCK_NONE = 0xFFFFFFFF     # MGENX_CLOCK_NONE

@@ -432,6 +432,23 @@ int mgenx_msg_match(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                     uint32_t* dev_send_first_rx, uint32_t* dev_recv_send,
                     struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
                     void* stream) {
+  return mgenx_msg_match_ex(ctx, dev_send_flow_idx, dev_send_seq, dev_send_t_sec, dev_send_t_usec,
+                            dev_send_len, ns, dev_recv_flow_idx, dev_recv_seq, dev_recv_tx_sec,
+                            dev_recv_tx_usec, dev_recv_rx_sec, dev_recv_rx_usec, nr, n_flows, opts,
+                            dev_send_rx_count, dev_send_first_rx, dev_recv_send, dev_flows,
+                            dev_stats, nullptr, stream);
+}
+
+int mgenx_msg_match_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                       const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                       const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len, uint32_t ns,
+                       const uint32_t* dev_recv_flow_idx, const uint32_t* dev_recv_seq,
+                       const uint32_t* dev_recv_tx_sec, const uint32_t* dev_recv_tx_usec,
+                       const uint32_t* dev_recv_rx_sec, const uint32_t* dev_recv_rx_usec,
+                       uint32_t nr, uint32_t n_flows, uint32_t opts, uint32_t* dev_send_rx_count,
+                       uint32_t* dev_send_first_rx, uint32_t* dev_recv_send,
+                       struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
+                       const mgenx_match_timeline* tl, void* stream) {
   if (!ctx || !dev_stats || ns > (1u << 30) || nr > 0x7FFFFFFFu || n_flows > 0x7FFFFFFFu)
     return MGENX_EINVAL;
   if (ns && (!dev_send_flow_idx || !dev_send_seq || !dev_send_t_sec || !dev_send_t_usec ||
@@ -441,13 +458,21 @@ int mgenx_msg_match(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
              !dev_recv_rx_sec || !dev_recv_rx_usec || !dev_recv_send))
     return MGENX_EINVAL;
   if (n_flows && !dev_flows) return MGENX_EINVAL;
+  if (tl && tl->n_bins) {
+    const int64_t lim = (int64_t)1 << 62;
+    if (tl->width_us == 0 || tl->t0_us < -lim || tl->t0_us > lim ||
+        (uint64_t)n_flows * tl->n_bins >= (1ull << 31) ||
+        (n_flows && (!tl->dev_bins || !tl->dev_outside)))
+      return MGENX_EINVAL;
+  }
+  if (tl && tl->dev_n_runs && tl->run_cap && !tl->dev_runs) return MGENX_EINVAL;
   hipSetDevice(ctx->device);
   return mgenx::msg_match_run(ctx->match_ws, dev_send_flow_idx, dev_send_seq, dev_send_t_sec,
                              dev_send_t_usec, dev_send_len, ns, dev_recv_flow_idx, dev_recv_seq,
                              dev_recv_tx_sec, dev_recv_tx_usec, dev_recv_rx_sec, dev_recv_rx_usec,
                              nr, n_flows, opts, dev_send_rx_count, dev_send_first_rx,
-                             dev_recv_send, dev_flows, dev_stats, (hipStream_t)stream, ctx->err,
-                             sizeof(ctx->err));
+                             dev_recv_send, dev_flows, dev_stats, tl, (hipStream_t)stream,
+                             ctx->err, sizeof(ctx->err));
 }
 
 static int log_recv(mgenx_ctx* ctx, bool binary, const uint8_t* dev_slab, uint64_t slab_bytes,

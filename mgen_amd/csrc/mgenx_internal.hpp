@@ -235,7 +235,8 @@ int msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_seq, con
                   const uint32_t* r_txu, const uint32_t* r_rxs, const uint32_t* r_rxu, uint32_t nr,
                   uint32_t n_flows, uint32_t opts, uint32_t* send_rx_count, uint32_t* send_first_rx,
                   uint32_t* recv_send, struct mgenx_flow_match* flows,
-                  struct mgenx_match_stats* stats, hipStream_t stream, char* err, size_t errn);
+                  struct mgenx_match_stats* stats, const mgenx_match_timeline* tl,
+                  hipStream_t stream, char* err, size_t errn);
 
 // ---- mgenx_log.hip ----
 mgenx_log_ws* log_ws_new();

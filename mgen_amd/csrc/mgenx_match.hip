@@ -1,6 +1,6 @@
 // mgenx_match.hip -- a sender's log joined with a receiver's log on gfx950 (mgenx_msg_match,
-// mgenx_match_side; include/mgenx.h): an equi-join of two record sets on the message identity,
-// then per-flow delivery accounting in the sender's order.
+// mgenx_msg_match_ex, mgenx_match_side; include/mgenx.h): an equi-join of two record sets on the
+// message identity, then per-flow delivery accounting in the sender's order.
 //
 //   0. match_init_kernel writes the empty per-flow values, zeroes the global counters and
 //      empties the hash table;
@@ -31,6 +31,14 @@
 //      segmented scan; the 18 histogram counts ride along as 12-bit fields of four words) and
 //      go out as one atomic per field that is not its identity.  Integer sums, minima and
 //      maxima commute, so the bytes left do not depend on the order the workgroups finish in.
+//   5. mgenx_msg_match_ex's timeline, only when asked for: match_mark_kernel writes own[] into
+//      the caller's owner column; match_pack_kernel<true> also leaves each position's send stamp
+//      and a second chunk summary (the first and last U after the last segment start);
+//      match_series_kernel reduces the positions of one (flow, window of send time) that follow
+//      each other and adds them to the cell with atomics; match_carry_fl_kernel,
+//      match_runs_kernel<false>, match_run_base_kernel and match_runs_kernel<true> find each run
+//      where the main pass counts it, with its first and last U, count the listed ones per
+//      chunk, scan the counts and write the list in the order of the sorted positions.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
@@ -212,6 +220,10 @@ __global__ void match_probe_kernel(MatchSide send, MatchSide recv, uint32_t nr, 
 // `head` starts a segment at this lane.  Returns the sum of v over the lanes from the lane's
 // segment start (or lane 0) to the lane; *open = no segment starts at or before it.
 // s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
+struct SumOp {
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a + b; }
+};
+template <class Op>
 __device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t* s_v,
                                                  uint32_t* s_h, bool* open) {
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -221,7 +233,7 @@ __device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t
     const uint32_t pv = __shfl_up(v, d);
     const uint32_t ph = __shfl_up(h, d);
     if (lane >= d && !h) {
-      v += pv;
+      v = Op::of(pv, v);
       h = ph;
     }
   }
@@ -238,7 +250,7 @@ __device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t
       const uint32_t pv = __shfl_up(wv, d);
       const uint32_t ph = __shfl_up(wh, d);
       if (lane >= d && !wh) {
-        wv += pv;
+        wv = Op::of(pv, wv);
         wh = ph;
       }
     }
@@ -249,7 +261,7 @@ __device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t
   }
   __syncthreads();
   if (w > 0 && !h) {
-    v += s_v[w - 1];
+    v = Op::of(s_v[w - 1], v);
     h = s_h[w - 1];
   }
   *open = h == 0u;
@@ -264,16 +276,49 @@ __device__ __forceinline__ uint32_t run_word(uint8_t cls, bool head_flow, bool* 
   return (cls == kU ? 1u : 0u) | (head_flow ? kFromFlowStart : 0u);
 }
 
+// ---- the first and the last U of a loss run (mgenx_msg_match_ex's run list) ----
+// The scan of run_word's segments with another operator: a U at lane t is the word
+// (0x800 - t) << 16 | (t + 1), every other position 0 (no U), and the halves combine by maximum:
+// the high half ends as 0x800 - the lowest lane with a U, the low half as the highest + 1.
+struct FlOp {
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) {
+    const uint32_t ah = a & 0xFFFF0000u, bh = b & 0xFFFF0000u, al = a & 0xFFFFu, bl = b & 0xFFFFu;
+    return (ah > bh ? ah : bh) | (al > bl ? al : bl);
+  }
+};
+struct MinOp {
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a < b ? a : b; }
+};
+struct MaxOp {
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a > b ? a : b; }
+};
+__device__ __forceinline__ uint32_t fl_word(uint8_t cls, uint32_t t) {
+  return cls == kU ? ((0x800u - t) << 16) | (t + 1u) : 0u;
+}
+// sorted positions from a chunk's word: the first U (kEmpty: none) and the last U + 1 (0: none)
+__device__ __forceinline__ uint32_t fl_first(uint32_t w, uint32_t p0) {
+  const uint32_t h = (w >> 16) & 0xFFFu;
+  return h ? p0 + 0x800u - h : kEmpty;
+}
+__device__ __forceinline__ uint32_t fl_last1(uint32_t w, uint32_t p0) {
+  const uint32_t l = w & 0xFFFFu;
+  return l ? p0 + l : 0u;
+}
+
 struct PackCols {
   const uint32_t *own, *rx_count, *first_rx, *len, *t_sec, *t_usec, *rx_sec, *rx_usec;
 };
 
-// pass 4a: classify, pack, and the chunk's summary
+// pass 4a: classify, pack, and the chunk's summary.  kTimeline (mgenx_msg_match_ex with a series
+// or a run list): the position's send stamp rides along, and trail_fl[c] is the chunk's first
+// and last U after its last segment start (fl_word).
+template <bool kTimeline>
 __global__ void __launch_bounds__(kChunk)
 match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
                   const uint32_t* __restrict__ bnd, uint32_t n_flows, PackCols col,
                   MatchRec* __restrict__ rec, uint8_t* __restrict__ cls_out,
-                  uint32_t* __restrict__ trail, uint32_t* __restrict__ has_head) {
+                  uint32_t* __restrict__ trail, uint32_t* __restrict__ has_head,
+                  int64_t* __restrict__ stamp, uint32_t* __restrict__ trail_fl) {
   __shared__ uint32_t s_v[kWaves], s_h[kWaves];
   const uint32_t c = blockIdx.x, t = threadIdx.x;
   const uint32_t nv = bnd[n_flows];
@@ -282,6 +327,7 @@ match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     if (t == 0) {
       trail[c] = 0u;
       has_head[c] = 1u;
+      if (kTimeline) trail_fl[c] = 0u;
     }
     return;
   }
@@ -306,17 +352,23 @@ match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
         cls = kU;
       }
     }
+    // (a send duplicate's stamp places nothing: it only keeps the series' key runs whole)
+    if (kTimeline) stamp[p] = (int64_t)col.t_sec[i] * 1000000 + (int64_t)col.t_usec[i];
     rec[p] = r;
     cls_out[p] = cls;
     v = run_word(cls, p == bnd[f], &head);
   }
   bool open;
-  const uint32_t incl = block_segsum(v, head, s_v, s_h, &open);
+  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
   const int any = __syncthreads_or(active && head);
   const uint32_t last = (uint32_t)min((uint64_t)nv - p0, (uint64_t)kChunk) - 1u;
   if (t == last) {
     trail[c] = incl;
     has_head[c] = any ? 1u : 0u;
+  }
+  if (kTimeline) {
+    const uint32_t fl = block_segsum<FlOp>(fl_word(cls, t), head, s_v, s_h, &open);
+    if (t == last) trail_fl[c] = fl;
   }
 }
 
@@ -336,7 +388,7 @@ match_carry_kernel(const uint32_t* __restrict__ trail, const uint32_t* __restric
     uint32_t v = in ? trail[c] : 0u;
     const bool head = in ? has_head[c] != 0u : true;
     bool open;
-    v = block_segsum(v, head, s_v, s_h, &open);
+    v = block_segsum<SumOp>(v, head, s_v, s_h, &open);
     if (open) v += s_run;
     if (in) carry[c] = v;
     __syncthreads();  // every lane has read s_run
@@ -457,7 +509,7 @@ match_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
   }
   s_key[t] = f;
   bool open;
-  const uint32_t incl = block_segsum(v, head, s_v, s_h, &open);
+  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
   s_incl[t] = incl;
   __syncthreads();
 
@@ -525,6 +577,346 @@ match_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------
+// the timeline (mgenx_msg_match_ex): the series per send-time window and the run list.
+// Both read what passes 4a and 4b left (cls, MatchRec, the stamps, the carries) and run after
+// them, only when asked for.
+// ------------------------------------------------------------------------------------
+typedef struct mgenx_match_bin MatchBin;
+typedef struct mgenx_loss_run LossRun;
+static_assert(sizeof(MatchBin) == 64, "mgenx_match_bin is 64 B");
+static_assert(sizeof(LossRun) == 40, "mgenx_loss_run is 40 B");
+constexpr uint32_t kOutside = 1u << 31;  // a series key outside the windows: kOutside | flow
+
+// every cell, every outside count and the run count: written on every call
+__global__ void match_tl_init_kernel(MatchBin* bins, uint32_t n_cells, uint64_t* outside,
+                                     uint32_t n_flows, uint64_t* n_runs) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_cells) {
+    MatchBin b = {};
+    b.lat_min = INT64_MAX;
+    b.lat_max = INT64_MIN;
+    bins[i] = b;
+  }
+  if (i < n_flows && outside) outside[i] = 0ull;
+  if (i == 0 && n_runs) *n_runs = 0ull;
+}
+
+// the terms of one position, or of a run of positions of one (flow, window)
+struct SeriesAcc {
+  uint32_t cnt;  // sent | delivered << 16: at most kChunk each
+  uint64_t sent_bytes, delivered_bytes, rx_dup, lat_sum;
+  int64_t lat_min, lat_max;
+};
+__device__ __forceinline__ void sacc_add(SeriesAcc& a, const SeriesAcc& b) {
+  a.cnt += b.cnt;
+  a.sent_bytes += b.sent_bytes;
+  a.delivered_bytes += b.delivered_bytes;
+  a.rx_dup += b.rx_dup;
+  a.lat_sum += b.lat_sum;
+  a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
+  a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
+}
+__device__ __forceinline__ SeriesAcc sacc_shfl_up(const SeriesAcc& a, uint32_t d) {
+  typedef unsigned long long ull;
+  SeriesAcc o;
+  o.cnt = __shfl_up(a.cnt, d);
+  o.sent_bytes = __shfl_up((ull)a.sent_bytes, d);
+  o.delivered_bytes = __shfl_up((ull)a.delivered_bytes, d);
+  o.rx_dup = __shfl_up((ull)a.rx_dup, d);
+  o.lat_sum = __shfl_up((ull)a.lat_sum, d);
+  o.lat_min = __shfl_up((long long)a.lat_min, d);
+  o.lat_max = __shfl_up((long long)a.lat_max, d);
+  return o;
+}
+// segmented inclusive scan of the terms over the kChunk lanes (block_segscan's shape)
+__device__ __forceinline__ void block_series_scan(SeriesAcc& a, bool head, SeriesAcc* s_a,
+                                                  uint32_t* s_h) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint32_t h = head ? 1u : 0u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const SeriesAcc pa = sacc_shfl_up(a, d);
+    const uint32_t ph = __shfl_up(h, d);
+    if (lane >= d && !h) {
+      sacc_add(a, pa);
+      h = ph;
+    }
+  }
+  if (lane == 63u) {
+    s_a[w] = a;
+    s_h[w] = h;
+  }
+  __syncthreads();
+  if (w == 0) {
+    SeriesAcc wa = s_a[lane < kWaves ? lane : 0u];
+    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
+#pragma unroll
+    for (uint32_t d = 1; d < kWaves; d <<= 1) {
+      const SeriesAcc pa = sacc_shfl_up(wa, d);
+      const uint32_t ph = __shfl_up(wh, d);
+      if (lane >= d && !wh) {
+        sacc_add(wa, pa);
+        wh = ph;
+      }
+    }
+    if (lane < kWaves) s_a[lane] = wa;
+  }
+  __syncthreads();
+  if (w > 0 && !h) sacc_add(a, s_a[w - 1]);  // the run started in an earlier wave
+}
+
+// the series.  A lane per sorted position; the positions of one (flow, window) that follow each
+// other are reduced on chip and leave one atomic per field that is not its identity.  A cell
+// that comes up again (a log out of time order, a later chunk) is combined by those atomics.
+__global__ void __launch_bounds__(kChunk)
+match_series_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ bnd,
+                    uint32_t n_flows, const MatchRec* __restrict__ rec,
+                    const uint8_t* __restrict__ cls_in, const int64_t* __restrict__ stamp,
+                    int64_t t0, uint64_t width, uint32_t n_bins, MatchBin* bins,
+                    uint64_t* outside) {
+  typedef unsigned long long ull;
+  __shared__ uint32_t s_key[kChunk];
+  __shared__ uint32_t s_h[kWaves];
+  __shared__ SeriesAcc s_a[kWaves];
+
+  const uint32_t c = blockIdx.x, t = threadIdx.x;
+  const uint32_t nv = bnd[n_flows];
+  const uint64_t p0 = (uint64_t)c * kChunk;
+  if (p0 >= nv) return;  // (the whole workgroup)
+  const uint32_t p = (uint32_t)p0 + t;
+  const bool active = p < nv;
+
+  uint32_t key = kEmpty, f = 0u;
+  SeriesAcc a = {0u, 0, 0, 0, 0, INT64_MAX, INT64_MIN};
+  if (active) {
+    f = keys[p];
+    const uint8_t cls = cls_in[p];
+    const MatchRec me = rec[p];
+    // t0 lies in [-2^62, 2^62] and a stamp in [0, 2^53): the difference fits; a negative floor
+    // is outside whatever its value
+    const int64_t d = stamp[p] - t0;
+    const uint64_t b = d < 0 ? (uint64_t)n_bins : (uint64_t)d / width;
+    key = b < n_bins ? f * n_bins + (uint32_t)b : kOutside | f;
+    if (cls != kX) {
+      a.cnt = 1u;
+      a.sent_bytes = me.len;
+    }
+    if (cls == kD) {
+      a.cnt |= 1u << 16;
+      a.delivered_bytes = me.len;
+      a.rx_dup = me.rxc - 1u;
+      a.lat_sum = (uint64_t)me.lat;
+      a.lat_min = a.lat_max = me.lat;
+    }
+  }
+  s_key[t] = key;
+  __syncthreads();
+  const bool run_head = !active || t == 0u || s_key[t - 1u] != key;
+  const bool run_tail = active && (t == kChunk - 1u || s_key[t + 1u] != key);
+  block_series_scan(a, run_head, s_a, s_h);
+
+  if (run_tail) {
+    const uint32_t sent = a.cnt & 0xFFFFu, dlv = a.cnt >> 16;
+    if (key & kOutside) {
+      if (sent) atomicAdd((ull*)&outside[f], (ull)sent);
+    } else if (sent) {
+      MatchBin* d = bins + key;
+      atomicAdd((ull*)&d->sent, (ull)sent);
+      if (a.sent_bytes) atomicAdd((ull*)&d->sent_bytes, (ull)a.sent_bytes);
+      if (dlv) {
+        atomicAdd((ull*)&d->delivered, (ull)dlv);
+        if (a.delivered_bytes) atomicAdd((ull*)&d->delivered_bytes, (ull)a.delivered_bytes);
+        if (a.rx_dup) atomicAdd((ull*)&d->rx_dup, (ull)a.rx_dup);
+        if (a.lat_sum) atomicAdd((ull*)&d->lat_sum, (ull)a.lat_sum);
+        atomicMin((long long*)&d->lat_min, (long long)a.lat_min);
+        atomicMax((long long*)&d->lat_max, (long long)a.lat_max);
+      }
+    }
+  }
+}
+
+// (one workgroup) over the chunks, as match_carry_kernel: carry_first[c] / carry_last1[c] = the
+// sorted position of the first U and of the last U + 1 (kEmpty / 0: none) in the segment that
+// is open after chunk c's last position
+__global__ void __launch_bounds__(kChunk)
+match_carry_fl_kernel(const uint32_t* __restrict__ trail_fl, const uint32_t* __restrict__ has_head,
+                      uint32_t n_chunks, uint32_t* __restrict__ carry_first,
+                      uint32_t* __restrict__ carry_last1) {
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  __shared__ uint32_t s_first, s_last1;
+  const uint32_t t = threadIdx.x;
+  if (t == 0) {
+    s_first = kEmpty;
+    s_last1 = 0u;
+  }
+  __syncthreads();
+  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
+    const uint32_t c = base + t;
+    const bool in = c < n_chunks;
+    const uint32_t w = in ? trail_fl[c] : 0u;
+    const bool head = in ? has_head[c] != 0u : true;
+    bool open;
+    uint32_t first = block_segsum<MinOp>(fl_first(w, c * kChunk), head, s_v, s_h, &open);
+    uint32_t last1 = block_segsum<MaxOp>(fl_last1(w, c * kChunk), head, s_v, s_h, &open);
+    if (open) {
+      first = MinOp::of(s_first, first);
+      last1 = MaxOp::of(s_last1, last1);
+    }
+    if (in) {
+      carry_first[c] = first;
+      carry_last1[c] = last1;
+    }
+    __syncthreads();  // every lane has read s_first / s_last1
+    if (t == kChunk - 1u) {
+      s_first = first;
+      s_last1 = last1;
+    }
+    __syncthreads();
+  }
+}
+
+// the run list.  A run is found where match_main_kernel counts it: at the D that follows it or
+// at its flow's last position, so the list's order is the order of the sorted positions: by
+// flow, then by send index.  kWrite false: chunk_n[c] = the listed runs that end in chunk c.
+// kWrite true (after match_run_base_kernel): each is written at chunk_base[c] + its rank in the
+// chunk, unless the list does not fit.
+template <bool kWrite>
+__global__ void __launch_bounds__(kChunk)
+match_runs_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
+                  const uint32_t* __restrict__ bnd, uint32_t n_flows,
+                  const uint8_t* __restrict__ cls_in, const int64_t* __restrict__ stamp,
+                  const uint32_t* __restrict__ carry, const uint32_t* __restrict__ carry_first,
+                  const uint32_t* __restrict__ carry_last1, uint32_t min_run,
+                  uint32_t* __restrict__ chunk_n, const uint32_t* __restrict__ chunk_base,
+                  const uint64_t* __restrict__ n_runs, LossRun* __restrict__ runs,
+                  uint64_t run_cap) {
+  __shared__ uint32_t s_incl[kChunk], s_fl[kChunk];
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  __shared__ uint32_t s_cin[3];
+
+  const uint32_t c = blockIdx.x, t = threadIdx.x;
+  const uint32_t nv = bnd[n_flows];
+  const uint64_t p0 = (uint64_t)c * kChunk;
+  if (p0 >= nv) {  // (the whole workgroup)
+    if (!kWrite && t == 0) chunk_n[c] = 0u;
+    return;
+  }
+  if (kWrite && *n_runs > run_cap) return;  // too small a list: not one byte of it changes
+  const uint32_t p = (uint32_t)p0 + t;
+  const bool active = p < nv;
+
+  uint32_t f = kEmpty;
+  uint8_t cls = kX;
+  bool head_flow = false, tail_flow = false, head = true;
+  uint32_t v = 0u;
+  if (t == 0u) {
+    s_cin[0] = 0u;
+    s_cin[1] = kEmpty;
+    s_cin[2] = 0u;
+  }
+  if (active) {
+    f = keys[p];
+    head_flow = p == bnd[f];
+    tail_flow = p == bnd[f + 1u] - 1u;
+    cls = cls_in[p];
+    v = run_word(cls, head_flow, &head);
+    // the chunk's first position inside a flow continues the chunks before it (c > 0)
+    if (t == 0u && !head_flow) {
+      s_cin[0] = carry[c - 1u];
+      s_cin[1] = carry_first[c - 1u];
+      s_cin[2] = carry_last1[c - 1u];
+      if (cls != kD) v += s_cin[0];
+    }
+  }
+  bool open, open_fl;
+  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
+  const uint32_t fl = block_segsum<FlOp>(fl_word(cls, t), head, s_v, s_h, &open_fl) |
+                      (open_fl ? 1u << 31 : 0u);  // bit 31: the segment began before the chunk
+  s_incl[t] = incl;
+  s_fl[t] = fl;
+  __syncthreads();
+
+  uint32_t ended = 0u, first = kEmpty, last1 = 0u;
+  if (active) {
+    uint32_t w = 0u;
+    bool local = false;
+    if (cls == kD) {
+      if (!head_flow) {
+        if (t == 0u) {
+          ended = s_cin[0];
+          first = s_cin[1];
+          last1 = s_cin[2];
+        } else {
+          ended = s_incl[t - 1u];
+          w = s_fl[t - 1u];
+          local = true;
+        }
+      }
+    } else if (tail_flow) {
+      ended = incl;
+      w = fl;
+      local = true;
+    }
+    if (local) {
+      first = fl_first(w, (uint32_t)p0);
+      last1 = fl_last1(w, (uint32_t)p0);
+      if (w >> 31) {
+        first = MinOp::of(s_cin[1], first);
+        last1 = MaxOp::of(s_cin[2], last1);
+      }
+    }
+  }
+  const uint32_t run = ended & kLenMask;
+  // (a run has a U: first and last1 - 1 are positions below nv; the test keeps a wrong carry
+  // from becoming a wild read)
+  const bool listed = run >= min_run && first < nv && last1 - 1u < nv;
+  if (!kWrite) {
+    const int n = __syncthreads_count(listed);
+    if (t == 0u) chunk_n[c] = (uint32_t)n;
+    return;
+  }
+  const uint32_t rank1 = block_segsum<SumOp>(listed ? 1u : 0u, t == 0u, s_v, s_h, &open);
+  if (listed) {
+    const uint64_t at = (uint64_t)chunk_base[c] + rank1 - 1u;
+    if (at < run_cap) {
+      LossRun r;
+      r.flow_idx = f;
+      r.length = run;
+      r.first_send = order[first];
+      r.last_send = order[last1 - 1u];
+      r.flags = ((ended & kFromFlowStart) ? MGENX_RUN_HEAD : 0u) |
+                (cls != kD ? MGENX_RUN_TAIL : 0u);
+      r.rsv = 0u;
+      r.t_first_us = stamp[first];
+      r.t_last_us = stamp[last1 - 1u];
+      runs[at] = r;
+    }
+  }
+}
+
+// (one workgroup) chunk_base[c] = the listed runs of the chunks before c; *n_runs = all of them
+__global__ void __launch_bounds__(kChunk)
+match_run_base_kernel(const uint32_t* __restrict__ chunk_n, uint32_t n_chunks,
+                      uint32_t* __restrict__ chunk_base, uint64_t* n_runs) {
+  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
+  __shared__ uint32_t s_sum;
+  const uint32_t t = threadIdx.x;
+  if (t == 0) s_sum = 0u;
+  __syncthreads();
+  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
+    const uint32_t c = base + t;
+    const uint32_t n = c < n_chunks ? chunk_n[c] : 0u;
+    bool open;
+    const uint32_t incl = block_segsum<SumOp>(n, t == 0u, s_v, s_h, &open) + s_sum;
+    if (c < n_chunks) chunk_base[c] = incl - n;
+    __syncthreads();  // every lane has read s_sum
+    if (t == kChunk - 1u) s_sum = incl;
+    __syncthreads();
+  }
+  if (t == 0) *n_runs = s_sum;
+}
+
 // one lane per parsed line (mgenx_match_side; src_out may be src)
 __global__ void match_side_kernel(const uint8_t* __restrict__ event,
                                   const uint8_t* __restrict__ status, const mgenx_addr* src,
@@ -563,7 +955,11 @@ int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_s
                          const uint32_t* r_rxu, uint32_t nr, uint32_t n_flows, uint32_t opts,
                          uint32_t* send_rx_count, uint32_t* send_first_rx, uint32_t* recv_send,
                          struct mgenx_flow_match* flows, struct mgenx_match_stats* stats,
-                         hipStream_t stream, char* err, size_t errn) {
+                         const mgenx_match_timeline* tl, hipStream_t stream, char* err,
+                         size_t errn) {
+  // the timeline's parts; with none of them the launches and the bytes are mgenx_msg_match's
+  const bool series = tl && tl->n_bins > 0, listed = tl && tl->dev_n_runs;
+  const bool timeline = series || listed;
   uint32_t n_slots = 64;  // a power of two >= 2 ns
   while (n_slots < 2u * ns) n_slots <<= 1;
   const bool account = ns > 0 && n_flows > 0;
@@ -572,7 +968,8 @@ int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_s
                sort_b = account ? a256(mgenx::flow_sort_ws(ns, n_flows)) : 0,
                rec_b = a256((size_t)ns * sizeof(MatchRec)), cls_b = a256((size_t)ns),
                c4 = a256((size_t)n_chunks * 4u);
-  const size_t need = tab_b + own_b + sort_b + rec_b + cls_b + 3 * c4;
+  const size_t stamp_b = timeline ? a256((size_t)ns * 8u) : 0, tl4 = timeline ? c4 : 0;
+  const size_t need = tab_b + own_b + sort_b + rec_b + cls_b + 3 * c4 + stamp_b + 5 * tl4;
   if (ws.reserve(need) != hipSuccess) {
     snprintf(err, errn, "msg_match: workspace of %zu bytes", need);
     return MGENX_EDEVICE;
@@ -586,6 +983,13 @@ int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_s
   uint32_t* trail = (uint32_t*)take(c4);
   uint32_t* has_head = (uint32_t*)take(c4);
   uint32_t* carry = (uint32_t*)take(c4);
+  int64_t* stamp = (int64_t*)take(stamp_b);
+  uint32_t* trail_fl = (uint32_t*)take(tl4);
+  uint32_t* carry_first = (uint32_t*)take(tl4);
+  uint32_t* carry_last1 = (uint32_t*)take(tl4);
+  uint32_t* chunk_n = (uint32_t*)take(tl4);
+  uint32_t* chunk_base = (uint32_t*)take(tl4);
+  if (tl && tl->dev_send_owner && ns) own = tl->dev_send_owner;  // the owner column, in place
 
   const bool use_time = !(opts & MGENX_MATCH_NO_TIME);
   const uint32_t mask = n_slots - 1u;
@@ -603,6 +1007,14 @@ int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_s
     hipLaunchKernelGGL(match_probe_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, stream, send,
                        recv, nr, n_flows, use_time, table, mask, send_rx_count, send_first_rx,
                        recv_send, flows, stats);
+  if (timeline) {
+    const uint32_t n_cells = series ? n_flows * tl->n_bins : 0u;
+    const uint32_t n_tl = n_cells > n_flows ? n_cells : n_flows ? n_flows : 1u;
+    hipLaunchKernelGGL(match_tl_init_kernel, dim3((n_tl + 255u) / 256u), dim3(256), 0, stream,
+                       series ? tl->dev_bins : nullptr, n_cells,
+                       series ? tl->dev_outside : nullptr, n_flows,
+                       listed ? tl->dev_n_runs : nullptr);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     snprintf(err, errn, "msg_match: %s", hipGetErrorString(e));
@@ -614,12 +1026,35 @@ int mgenx::msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_s
                                      err, errn);
   if (rc != MGENX_OK) return rc;
   const PackCols col = {own, send_rx_count, send_first_rx, s_len, s_sec, s_usec, r_rxs, r_rxu};
-  hipLaunchKernelGGL(match_pack_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, order, bnd,
-                     n_flows, col, rec, cls, trail, has_head);
+  if (timeline)
+    hipLaunchKernelGGL(match_pack_kernel<true>, dim3(n_chunks), dim3(kChunk), 0, stream, keys,
+                       order, bnd, n_flows, col, rec, cls, trail, has_head, stamp, trail_fl);
+  else
+    hipLaunchKernelGGL(match_pack_kernel<false>, dim3(n_chunks), dim3(kChunk), 0, stream, keys,
+                       order, bnd, n_flows, col, rec, cls, trail, has_head, (int64_t*)nullptr,
+                       (uint32_t*)nullptr);
   hipLaunchKernelGGL(match_carry_kernel, dim3(1), dim3(kChunk), 0, stream, trail, has_head,
                      n_chunks, carry);
   hipLaunchKernelGGL(match_main_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, bnd,
                      n_flows, rec, cls, carry, flows);
+  if (series)
+    hipLaunchKernelGGL(match_series_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, bnd,
+                       n_flows, rec, cls, stamp, tl->t0_us, tl->width_us, tl->n_bins, tl->dev_bins,
+                       tl->dev_outside);
+  if (listed) {
+    const uint32_t min_run = tl->min_run ? tl->min_run : 1u;
+    hipLaunchKernelGGL(match_carry_fl_kernel, dim3(1), dim3(kChunk), 0, stream, trail_fl, has_head,
+                       n_chunks, carry_first, carry_last1);
+    hipLaunchKernelGGL(match_runs_kernel<false>, dim3(n_chunks), dim3(kChunk), 0, stream, keys,
+                       order, bnd, n_flows, cls, stamp, carry, carry_first, carry_last1, min_run,
+                       chunk_n, chunk_base, tl->dev_n_runs, tl->dev_runs, tl->run_cap);
+    hipLaunchKernelGGL(match_run_base_kernel, dim3(1), dim3(kChunk), 0, stream, chunk_n, n_chunks,
+                       chunk_base, tl->dev_n_runs);
+    if (tl->run_cap)
+      hipLaunchKernelGGL(match_runs_kernel<true>, dim3(n_chunks), dim3(kChunk), 0, stream, keys,
+                         order, bnd, n_flows, cls, stamp, carry, carry_first, carry_last1, min_run,
+                         chunk_n, chunk_base, tl->dev_n_runs, tl->dev_runs, tl->run_cap);
+  }
   e = hipGetLastError();
   if (e != hipSuccess) {
     snprintf(err, errn, "msg_match: %s", hipGetErrorString(e));
