@@ -11,14 +11,15 @@ NAMES := mgenx_api mgenx_ctx mgenx_unpack mgenx_unpack_fixed mgenx_probe \
          mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_binlog mgenx_comm mgenx_worker \
          mgenx_worker_host mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse \
          mgenx_flowdist mgenx_defrag mgenx_pcap_tcp mgenx_flowseries mgenx_match \
-         mgenx_flowquant mgenx_flowclock
+         mgenx_flowquant mgenx_flowclock mgenx_matchmulti
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_internal.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
        mgen_amd/csrc/mgenx_unpack_long.hpp mgen_amd/csrc/mgenx_flowsm.hpp \
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \
        mgen_amd/csrc/mgenx_flowdist.hpp mgen_amd/csrc/mgenx_capture.hpp \
-       mgen_amd/csrc/mgenx_flowquant.hpp mgen_amd/csrc/mgenx_flowclock.hpp
+       mgen_amd/csrc/mgenx_flowquant.hpp mgen_amd/csrc/mgenx_flowclock.hpp \
+       mgen_amd/csrc/mgenx_match.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))
 DOBJ := $(addprefix build/diag/,$(addsuffix .o,$(NAMES)))
 LIBS := -L/opt/rocm/lib -lrccl -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
@@ -29,7 +30,7 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
      tests/cpp/flow_series_host tests/cpp/msg_match_host tests/cpp/flow_quant_host \
      tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host \
-     tests/cpp/match_timeline_host
+     tests/cpp/match_timeline_host tests/cpp/msg_match_multi_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -137,6 +138,11 @@ tests/cpp/msg_match_host: tests/cpp/msg_match_host.cpp include/mgenx.hpp include
 # mgenx::MessageMatch::RunTimeline (the series per send-time window, the loss runs, the owner
 # column) against a serial loop in the program
 tests/cpp/match_timeline_host: tests/cpp/match_timeline_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
+	$(HOSTCXX) $< -o $@ $(HOSTLD)
+
+# mgenx::MessageMatchMulti::RunSeries (one sender, five receivers) against a serial loop in the
+# program
+tests/cpp/msg_match_multi_host: tests/cpp/msg_match_multi_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
 	$(HOSTCXX) $< -o $@ $(HOSTLD)
 
 # mgenx::Pcap2Mgen with PcapOptions::tcp over a capture file (tests/test_gpu_pcap_tcp_cpp.py)

@@ -1614,6 +1614,97 @@ int mgenx_msg_match_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                        struct mgenx_flow_match* dev_flows, struct mgenx_match_stats* dev_stats,
                        const mgenx_match_timeline* tl, void* stream);
 
+/* ---- one sender's log joined with many receivers' logs: the delivery matrix ----
+ * A multicast run (doc/example.mgn: the flows go to 224.225.1.2 and every listener JOINs it) has
+ * one sender log and a log per receiver.  mgenx_msg_match_multi joins them in one call: which
+ * receivers got each message, the exact loss per (flow, receiver) with what a late joiner
+ * missed at the head, and how many messages reached all, some or none of the group over send
+ * time.  No reference code: this block is the contract.  Integer arithmetic only; every output
+ * byte is written on every call (no init call) and is a function of the inputs alone.
+ *
+ * Inputs: the send columns of mgenx_msg_match (flow_idx seq t_sec t_usec len, ns records) and
+ * its recv columns plus dev_recv_rcv (u32, the receiver's index): nr records, the receivers'
+ * logs one after the other, or in any other order.  n_rcv is 1..64; opts 0 or
+ * MGENX_MATCH_NO_TIME.  Identity, owner, send duplicate and counted / skipped send record are
+ * mgenx_msg_match's.  A recv record is counted iff flow_idx < n_flows and rcv < n_rcv; else it
+ * is skipped and adds to stats.recv_skipped.  An owner is delivered to r iff at least one
+ * counted recv record has its identity and rcv == r; its first arrival at r is the lowest-index
+ * such record.
+ *
+ * Per send record i: dev_send_mask[i] (u64) has bit r set iff i is an owner delivered to r; 0 for
+ * a send duplicate or a skipped record.
+ * Per recv record j: dev_recv_send[j] = the owner's index or MGENX_MATCH_NONE (skipped or no
+ * owner); dev_recv_first[j] (u8) = 1 iff the record is counted, has an owner and is that owner's
+ * first arrival at its receiver, else 0.
+ * dev_cells[f * n_rcv + r], struct mgenx_rcv_cell:
+ *   delivered, delivered_bytes  owners of f delivered to r; the sum of their len
+ *   rx_dup                      counted recv records of (f, r) that have an owner, minus delivered
+ *   rx_orphan                   counted recv records of (f, r) with no owner
+ *   lost_head                   owners of f before, in send-log order, the first owner delivered
+ *                               to r; the flow's sent when none was
+ *   lost_tail                   owners after the last owner delivered to r; 0 when none was
+ *   first_send, last_send       the send-record indices of those two owners, or MGENX_MATCH_NONE
+ *   lat_sum, lat_min, lat_max   signed 64-bit microseconds over the owners delivered to r: the rx
+ *                               stamp of the first arrival at r minus the owner's send stamp,
+ *                               widened as mgenx_msg_match_ex states; INT64_MAX / INT64_MIN in
+ *                               an empty cell; the sum wraps
+ * The loss at r is sent - delivered; its middle part sent - delivered - lost_head - lost_tail.
+ * dev_fanout[f], struct mgenx_flow_fanout: sent, sent_bytes, send_dup as in mgenx_flow_match;
+ * deliveries = the sum over the owners of popcount(mask); reached_all = owners whose mask has
+ * all n_rcv bits; reach_hist[k] = owners with popcount(mask) == k (0 above n_rcv).
+ * dev_stats: send_skipped, recv_skipped, recv_unmatched (counted recv records with no owner),
+ * send_dup.
+ *
+ * Series (tl non-null and n_bins > 0): the windows of send time are mgenx_msg_match_ex's (signed
+ * floor; dev_outside[f] counts the owners outside them).  dev_bins[f * n_bins + b], struct
+ * mgenx_multi_bin, over the owners in the window: sent, sent_bytes; deliveries (the sum of
+ * popcount) and delivered_bytes (len x popcount); reached_any (popcount > 0), reached_all;
+ * reach_min / reach_max, the least and greatest popcount (UINT64_MAX and 0 in an empty cell).
+ *
+ * There is no run list and there are no per-receiver loss runs: mgenx_msg_match_ex on one
+ * receiver's records gives those.
+ *
+ * Asynchronous; ns == 0, nr == 0 and n_flows == 0 are legal.  The workspace is the context's,
+ * shared with mgenx_msg_match (one stream at a time per context; it synchronises only to grow):
+ * 12 to 20 bytes per send record plus the stable sort's share (about 64 in all), 8 to 16 bytes
+ * per recv record (the (owner, receiver) table: a power of two >= 2 nr slots of 4 B), 16 bytes
+ * per cell and 12 per 1024 send records.  MGENX_EINVAL, before any HIP call: n_rcv outside
+ * 1..64; ns or nr above 2^30; n_flows * n_rcv or n_flows * n_bins >= 2^31; with n_bins > 0 a
+ * width_us of 0 or a t0_us outside [-2^62, 2^62]; a null required pointer (the columns and
+ * per-record outputs of an empty side and, with n_flows == 0, dev_cells, dev_fanout, dev_bins
+ * and dev_outside may be null). */
+struct mgenx_rcv_cell {      /* 80 B; one per (flow, receiver) */
+  uint64_t delivered, delivered_bytes, rx_dup, rx_orphan, lost_head, lost_tail;
+  uint32_t first_send, last_send;
+  int64_t  lat_sum, lat_min, lat_max;
+};
+struct mgenx_flow_fanout {   /* 560 B */
+  uint64_t sent, sent_bytes, send_dup, deliveries, reached_all;
+  uint64_t reach_hist[65];
+};
+struct mgenx_multi_bin {     /* 64 B; one per (flow, window of send time) */
+  uint64_t sent, sent_bytes, deliveries, delivered_bytes, reached_any, reached_all;
+  uint64_t reach_min, reach_max;        /* UINT64_MAX / 0 while sent == 0 */
+};
+typedef struct {             /* HOST struct */
+  int64_t  t0_us; uint64_t width_us; uint32_t n_bins;   /* n_bins == 0: no series */
+  struct mgenx_multi_bin* dev_bins;    /* [n_flows * n_bins], row f = flow f */
+  uint64_t* dev_outside;               /* [n_flows] */
+} mgenx_multi_timeline;
+int mgenx_msg_match_multi(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                          const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                          const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len,
+                          uint32_t ns, const uint32_t* dev_recv_flow_idx,
+                          const uint32_t* dev_recv_seq, const uint32_t* dev_recv_tx_sec,
+                          const uint32_t* dev_recv_tx_usec, const uint32_t* dev_recv_rx_sec,
+                          const uint32_t* dev_recv_rx_usec, const uint32_t* dev_recv_rcv,
+                          uint32_t nr, uint32_t n_rcv, uint32_t n_flows, uint32_t opts,
+                          uint64_t* dev_send_mask, uint32_t* dev_recv_send,
+                          uint8_t* dev_recv_first, struct mgenx_rcv_cell* dev_cells,
+                          struct mgenx_flow_fanout* dev_fanout,
+                          struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
+                          void* stream);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ----
  * One communicator per rank (one process per GPU): rank 0 calls mgenx_comm_unique_id and
  * hands the MGENX_COMM_ID_BYTES bytes to every rank (any out-of-band channel), then every

@@ -884,6 +884,97 @@ class MessageMatch {
   DeviceArray<uint32_t> own_;
 };
 
+// ---- one sender's log joined with many receivers' logs: the delivery matrix -------------------
+// mgenx_msg_match_multi (include/mgenx.h) over host columns: MessageMatch's send and recv columns
+// plus the receiver's index of every recv record, the receivers' records one after the other.
+// One Run per set of logs; the results stay on the device until they are asked for.
+class MessageMatchMulti {
+ public:
+  typedef struct mgenx_rcv_cell Cell;
+  typedef struct mgenx_flow_fanout FlowFanout;
+  typedef struct mgenx_match_stats MatchStats;
+  typedef struct mgenx_multi_bin Bin;
+  typedef MessageMatch::SendColumns SendColumns;
+  typedef MessageMatch::RecvColumns RecvColumns;
+  // nRcv: 1..64; opts: 0 or MGENX_MATCH_NO_TIME
+  MessageMatchMulti(Context& ctx, uint32_t nFlows, uint32_t nRcv, uint32_t opts = 0)
+      : ctx_(ctx), n_flows_(nFlows), n_rcv_(nRcv), opts_(opts), cells_((size_t)nFlows * nRcv),
+        fanout_(nFlows), stats_(1) {}
+  void Run(const SendColumns& s, const RecvColumns& r, const std::vector<uint32_t>& rcv) {
+    RunSeries(s, r, rcv, 0, 1, 0);
+  }
+  // Run plus the series per window of send time: nBins windows of width_us from t0_us
+  void RunSeries(const SendColumns& s, const RecvColumns& r, const std::vector<uint32_t>& rcv,
+                 int64_t t0_us, uint64_t width_us, uint32_t nBins) {
+    ns_ = (uint32_t)s.flow_idx.size();
+    nr_ = (uint32_t)r.flow_idx.size();
+    const std::vector<uint32_t>* sc[5] = {&s.flow_idx, &s.seq, &s.t_sec, &s.t_usec, &s.len};
+    const std::vector<uint32_t>* rc[7] = {&r.flow_idx, &r.seq,     &r.tx_sec, &r.tx_usec,
+                                          &r.rx_sec,   &r.rx_usec, &rcv};
+    hipStream_t st = ctx_.stream();
+    for (int k = 0; k < 5; k++) Upload(d_s_[k], *sc[k], ns_, st);
+    for (int k = 0; k < 7; k++) Upload(d_r_[k], *rc[k], nr_, st);
+    mask_.Resize(ns_);
+    rs_.Resize(nr_);
+    first_.Resize(nr_);
+    n_bins_ = nBins;
+    bins_.Resize((size_t)n_flows_ * nBins);
+    outside_.Resize(nBins ? n_flows_ : 0);
+    mgenx_multi_timeline tl = {};
+    tl.t0_us = t0_us;
+    tl.width_us = width_us;
+    tl.n_bins = nBins;
+    tl.dev_bins = bins_.data();
+    tl.dev_outside = outside_.data();
+    ctx_.Check(mgenx_msg_match_multi(ctx_.get(), d_s_[0].data(), d_s_[1].data(), d_s_[2].data(),
+                                     d_s_[3].data(), d_s_[4].data(), ns_, d_r_[0].data(),
+                                     d_r_[1].data(), d_r_[2].data(), d_r_[3].data(),
+                                     d_r_[4].data(), d_r_[5].data(), d_r_[6].data(), nr_, n_rcv_,
+                                     n_flows_, opts_, mask_.data(), rs_.data(), first_.data(),
+                                     cells_.data(), fanout_.data(), stats_.data(),
+                                     nBins ? &tl : nullptr, st),
+               "mgenx_msg_match_multi");
+    ctx_.Sync();  // the host vectors are the caller's again
+  }
+  // row f, column r: element f * nRcv + r
+  std::vector<Cell> Cells() { return Download(cells_, (size_t)n_flows_ * n_rcv_); }
+  std::vector<FlowFanout> Fanout() { return Download(fanout_, n_flows_); }
+  MatchStats Stats() { return Download(stats_, 1)[0]; }
+  // per send record: bit r set iff it is an owner delivered to receiver r
+  std::vector<uint64_t> SendMask() { return Download(mask_, ns_); }
+  // per recv record: the send record it belongs to, or MGENX_MATCH_NONE; 1 for a first arrival
+  std::vector<uint32_t> RecvSend() { return Download(rs_, nr_); }
+  std::vector<uint8_t> RecvFirst() { return Download(first_, nr_); }
+  std::vector<Bin> Bins() { return Download(bins_, (size_t)n_flows_ * n_bins_); }  // row f = flow f
+  std::vector<uint64_t> Outside() { return Download(outside_, n_bins_ ? n_flows_ : 0); }
+
+ private:
+  void Upload(DeviceArray<uint32_t>& d, const std::vector<uint32_t>& h, uint32_t n,
+              hipStream_t st) {
+    if (h.size() != n) throw Error("MessageMatchMulti: columns of unequal length");
+    d.Resize(n);
+    if (n) check_hip(hipMemcpyAsync(d.data(), h.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "H2D");
+  }
+  template <typename T>
+  std::vector<T> Download(const DeviceArray<T>& d, size_t n) {
+    std::vector<T> out(n);
+    if (n)
+      check_hip(hipMemcpyAsync(out.data(), d.data(), n * sizeof(T), hipMemcpyDeviceToHost,
+                               ctx_.stream()), "D2H");
+    ctx_.Sync();
+    return out;
+  }
+  Context& ctx_;
+  uint32_t n_flows_, n_rcv_, opts_, ns_ = 0, nr_ = 0, n_bins_ = 0;
+  DeviceArray<Cell> cells_;
+  DeviceArray<FlowFanout> fanout_;
+  DeviceArray<MatchStats> stats_;
+  DeviceArray<uint32_t> d_s_[5], d_r_[7], rs_;
+  DeviceArray<uint64_t> mask_, outside_;
+  DeviceArray<uint8_t> first_;
+  DeviceArray<Bin> bins_;
+};
+
 // ---- per-flow clock offset and skew removal ------------------------------------------------
 // mgenx_flow_clock (include/mgenx.h) over host columns: per flow the edge of the lower hull of
 // (send time, latency) over the mean send time, per record the latency above that line.  One Run

@@ -34,6 +34,7 @@ from ._abi import (  # noqa: F401
     MATCH_NONE, MATCH_NO_TIME, MATCH_RUN_BINS, FLOW_MATCH_DTYPE, MATCH_STATS_DTYPE,
     RUN_HEAD, RUN_TAIL, MATCH_BIN_DTYPE, LOSS_RUN_DTYPE, MatchTimeline,
     CLOCK_NONE, CLOCK_OFFSET_ONLY, FLOW_CLOCK_DTYPE,
+    MATCH_MAX_RCV, RCV_CELL_DTYPE, FLOW_FANOUT_DTYPE, MULTI_BIN_DTYPE, MultiTimeline,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
     "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock", "mgenx_msg_match_ex",
+    "mgenx_msg_match_multi",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -183,6 +185,8 @@ def load(diag: bool = False):
                                   P, P, P]
     L.mgenx_msg_match_ex.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, u32, u32, u32, P, P,
                                      P, P, P, ctypes.POINTER(MatchTimeline), P]
+    L.mgenx_msg_match_multi.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, P, u32, u32, u32,
+                                        u32, P, P, P, P, P, P, ctypes.POINTER(MultiTimeline), P]
     L.mgenx_flow_dist_bin.argtypes = [u64]
     L.mgenx_flow_dist_bin.restype = u32
     L.mgenx_flow_dist_bin_lo.argtypes = [u32]
@@ -784,6 +788,51 @@ class Engine:
             _ptr(flows), _ptr(stats), _stream(self.device)), "mgenx_msg_match")
         return (cnt[:ns], first[:ns], rs[:nr], flows[:n_flows * FLOW_MATCH_DTYPE.itemsize],
                 stats)
+
+    def msg_match_multi(self, n_flows, n_rcv, send, recv, *, opts=0, timeline=None, ns=None,
+                        nr=None):
+        """Join a sender's records with the records of n_rcv receivers (mgenx_msg_match_multi).
+        send: msg_match's dict; recv: msg_match's dict plus rcv (int32, the receiver's index of
+        every record), the receivers' records one after the other.  timeline: None or
+        (t0_us, width_us, n_bins), the windows of send time.  Returns (send_mask, recv_send,
+        recv_first, cells, fanout, stats): int64 [ns], int32 [nr], uint8 [nr], and uint8 tensors
+        of n_flows x n_rcv x 80 B (RCV_CELL_DTYPE), n_flows x 560 B (FLOW_FANOUT_DTYPE) and 32 B
+        (MATCH_STATS_DTYPE); with a timeline also bins (uint8, n_flows x n_bins x 64 B:
+        MULTI_BIN_DTYPE) and outside (int64, n_flows)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        ns = send["flow_idx"].numel() if ns is None else ns
+        nr = recv["flow_idx"].numel() if nr is None else nr
+        mask = torch.empty(max(ns, 1), dtype=torch.int64, device=dev)
+        rs = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(max(nr, 1), dtype=torch.uint8, device=dev)
+        n_cells = n_flows * n_rcv
+        cells = torch.empty(max(n_cells, 1) * RCV_CELL_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        fanout = torch.empty(max(n_flows, 1) * FLOW_FANOUT_DTYPE.itemsize, dtype=torch.uint8,
+                             device=dev)
+        stats = torch.empty(MATCH_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        tl, n_bins = None, 0
+        if timeline is not None:
+            t0_us, width_us, n_bins = (int(v) for v in timeline)
+            bins = torch.empty(max(n_flows * n_bins, 1) * MULTI_BIN_DTYPE.itemsize,
+                               dtype=torch.uint8, device=dev)
+            outside = torch.zeros(max(n_flows, 1), dtype=torch.int64, device=dev)
+            tl = ctypes.byref(MultiTimeline(t0_us=t0_us, width_us=width_us, n_bins=n_bins,
+                                            dev_bins=bins.data_ptr(),
+                                            dev_outside=outside.data_ptr()))
+        self._check(self.lib.mgenx_msg_match_multi(
+            self.ctx, _ptr(send["flow_idx"]), _ptr(send["seq"]), _ptr(send["t_sec"]),
+            _ptr(send["t_usec"]), _ptr(send["len"]), ns, _ptr(recv["flow_idx"]),
+            _ptr(recv["seq"]), _ptr(recv["tx_sec"]), _ptr(recv["tx_usec"]), _ptr(recv["rx_sec"]),
+            _ptr(recv["rx_usec"]), _ptr(recv["rcv"]), nr, n_rcv, n_flows, opts, _ptr(mask),
+            _ptr(rs), _ptr(first), _ptr(cells), _ptr(fanout), _ptr(stats), tl,
+            _stream(self.device)), "mgenx_msg_match_multi")
+        res = (mask[:ns], rs[:nr], first[:nr], cells[:n_cells * RCV_CELL_DTYPE.itemsize],
+               fanout[:n_flows * FLOW_FANOUT_DTYPE.itemsize], stats)
+        if timeline is not None:
+            res += (bins[:n_flows * n_bins * MULTI_BIN_DTYPE.itemsize], outside[:n_flows])
+        return res
 
     def msg_match_timeline(self, n_flows, send, recv, t0_us, width_us, n_bins, *, min_run=1,
                            opts=0, ns=None, nr=None):
@@ -1557,6 +1606,128 @@ def match_text_logs_timeline(send_log, recv_log, width_us, t0_us=None, n_bins=No
     enough for the highest (mgenx_flow_span over the sender's columns)."""
     tl = dict(width_us=int(width_us), t0_us=t0_us, n_bins=n_bins, min_run=int(min_run))
     return _match_text_logs(send_log, recv_log, no_time, day_base, device, tl)
+
+
+def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins=None,
+                          no_time=False, day_base=0, device=0) -> tuple:
+    """A sender's text log (SEND lines) joined with the text logs of several receivers (RECV
+    lines) on the GPU: every log goes through line index -> parse -> match_side, FindFlow runs
+    on one table (sender first, then the receivers in the order given), the receivers' columns
+    are concatenated with the receiver's index as a column, and mgenx_msg_match_multi joins
+    them.  Returns (keys, cells, fanout, stats, send_mask, n_send_flows): REPORT_KEY_DTYPE
+    [n_flows], RCV_CELL_DTYPE [n_flows, n_rcv], FLOW_FANOUT_DTYPE [n_flows], one
+    MATCH_STATS_DTYPE element, uint64 with one element per line of the sender's log (bit r: the
+    message reached receiver r), and the number of flows the sender's log has (receiver-only
+    flows follow).  With width_us also (bins, outside, t0_us): MULTI_BIN_DTYPE [n_flows, n_bins]
+    over windows of send time, uint64 [n_flows], and the first window's start; by default t0_us
+    is the lowest SEND stamp and n_bins just enough for the highest."""
+    import torch
+    recv_logs = list(recv_logs)
+    n_rcv = len(recv_logs)
+    if not 1 <= n_rcv <= MATCH_MAX_RCV:
+        raise ValueError(f"match_text_logs_multi: 1 to {MATCH_MAX_RCV} receiver logs")
+    eng = Engine(device)
+    table = None
+    try:
+        dev = f"cuda:{device}"
+
+        def side(log, want):
+            raw = np.frombuffer(bytes(log), np.uint8)
+            n = 0
+            if raw.size:
+                text = torch.from_numpy(raw.copy()).to(dev)
+                line_off, n = eng.text_index(text)
+            if n == 0:
+                return None, None, 0
+            p = eng.log_parse_text(text, line_off, n, day_base=day_base)
+            cols, src = eng.match_side(p, n, want)
+            return cols, src, n
+
+        s, s_src, ns = side(send_log, EVENT_SEND)
+        rsides = [side(log, EVENT_RECV) for log in recv_logs]
+        nr = sum(n for _, _, n in rsides)
+        none = torch.zeros(0, dtype=torch.int32, device=dev)
+        s_idx = none
+        r_idx = [none] * n_rcv
+        nf = n_send = 0
+        cap = max(ns + nr, 16)
+        while ns + nr:
+            # FLOW_NONE on an OK line means "redo on a larger table", never "no such flow"
+            table = eng.flow_table(cap)
+            refused = False
+            if ns:
+                s_idx, n_flows = eng.flow_lookup(table, s, s_src, ns)
+                n_send = int(n_flows.item())
+                refused = bool(((s["err"][:ns] == 0) & (s_idx == -1)).any().item())
+            nf = n_send
+            for k, (r, r_src, n) in enumerate(rsides):
+                if n and not refused:
+                    r_idx[k], n_flows = eng.flow_lookup(table, r, r_src, n)
+                    nf = int(n_flows.item())
+                    refused = bool(((r["err"][:n] == 0) & (r_idx[k] == -1)).any().item())
+            if not refused:
+                break
+            eng.flow_table_destroy(table)
+            table = None
+            cap *= 4
+        send = dict(flow_idx=s_idx, seq=none, t_sec=none, t_usec=none, len=none)
+        if ns:
+            send.update(seq=s["seq_num"], t_sec=s["rx_sec"], t_usec=s["rx_usec"], len=s["size"])
+        recv = dict(flow_idx=none, seq=none, tx_sec=none, tx_usec=none, rx_sec=none, rx_usec=none,
+                    rcv=none)
+        if nr:
+            live = [(k, r, n) for k, (r, _, n) in enumerate(rsides) if n]
+            cat = lambda name: torch.cat([r[name][:n].view(torch.int32)  # noqa: E731
+                                          for _, r, n in live])
+            recv.update(flow_idx=torch.cat([r_idx[k][:n] for k, _, n in live]),
+                        seq=cat("seq_num"), tx_sec=cat("tx_sec"), tx_usec=cat("tx_usec"),
+                        rx_sec=cat("rx_sec"), rx_usec=cat("rx_usec"),
+                        rcv=torch.repeat_interleave(
+                            torch.tensor([k for k, _, _ in live], dtype=torch.int32, device=dev),
+                            torch.tensor([n for _, _, n in live], device=dev)))
+        opts = MATCH_NO_TIME if no_time else 0
+        timeline = None
+        if width_us is not None:
+            width_us = int(width_us)
+            if t0_us is None or n_bins is None:
+                lo, hi = 2**64 - 1, 0
+                if ns and nf:
+                    _, lo, hi = eng.flow_span(s_idx, s["rx_sec"], s["rx_usec"], ns, nf)
+                if lo > hi:                  # no SEND line counts
+                    lo = hi = 0
+                if t0_us is None:
+                    t0_us = lo
+                if n_bins is None:
+                    n_bins = max((hi - int(t0_us)) // width_us + 1, 1)
+            t0_us, n_bins = int(t0_us), int(n_bins)
+            timeline = (t0_us, width_us, n_bins)
+        out = eng.msg_match_multi(nf, n_rcv, send, recv, opts=opts, timeline=timeline, ns=ns,
+                                  nr=nr)
+        mask, _rs, _first, cells, fanout, stats = out[:6]
+        keys = np.zeros(0, REPORT_KEY_DTYPE)
+        if nf:
+            proto = 1
+            for p in [s] + [r for r, _, _ in rsides]:
+                if p is not None:
+                    ok = p["protocol"][p["err"] == 0]
+                    if ok.numel():
+                        proto = int(ok[0].item())
+                        break
+            keys = eng.flow_keys(table, nf, protocol=proto).cpu().numpy().view(
+                REPORT_KEY_DTYPE)[:nf].copy()
+        torch.cuda.synchronize(device)
+        res = (keys, cells.cpu().numpy().view(RCV_CELL_DTYPE).reshape(nf, n_rcv).copy(),
+               fanout.cpu().numpy().view(FLOW_FANOUT_DTYPE).copy(),
+               stats.cpu().numpy().view(MATCH_STATS_DTYPE)[0].copy(),
+               mask.cpu().numpy().view(np.uint64).copy(), n_send)
+        if timeline is not None:
+            res += (out[6].cpu().numpy().view(MULTI_BIN_DTYPE).reshape(nf, n_bins).copy(),
+                    out[7].cpu().numpy().view(np.uint64).copy(), t0_us)
+        return res
+    finally:
+        if table is not None:
+            eng.flow_table_destroy(table)
+        eng.close()
 
 
 def _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, tl) -> tuple:

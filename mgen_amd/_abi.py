@@ -191,6 +191,28 @@ class MatchTimeline(ctypes.Structure):   # mgenx_match_timeline (a host struct)
                 ("dev_runs", ctypes.c_void_p), ("run_cap", ctypes.c_uint64),
                 ("dev_n_runs", ctypes.c_void_p), ("dev_send_owner", ctypes.c_void_p)]
 
+# ---- one sender's log joined with many receivers' logs (mgenx_msg_match_multi) ----
+MATCH_MAX_RCV = 64
+RCV_CELL_DTYPE = np.dtype([
+    ("delivered", "<u8"), ("delivered_bytes", "<u8"), ("rx_dup", "<u8"), ("rx_orphan", "<u8"),
+    ("lost_head", "<u8"), ("lost_tail", "<u8"), ("first_send", "<u4"), ("last_send", "<u4"),
+    ("lat_sum", "<i8"), ("lat_min", "<i8"), ("lat_max", "<i8")])
+FLOW_FANOUT_DTYPE = np.dtype([
+    ("sent", "<u8"), ("sent_bytes", "<u8"), ("send_dup", "<u8"), ("deliveries", "<u8"),
+    ("reached_all", "<u8"), ("reach_hist", "<u8", (MATCH_MAX_RCV + 1,))])
+MULTI_BIN_DTYPE = np.dtype([
+    ("sent", "<u8"), ("sent_bytes", "<u8"), ("deliveries", "<u8"), ("delivered_bytes", "<u8"),
+    ("reached_any", "<u8"), ("reached_all", "<u8"), ("reach_min", "<u8"), ("reach_max", "<u8")])
+assert (RCV_CELL_DTYPE.itemsize, FLOW_FANOUT_DTYPE.itemsize, MULTI_BIN_DTYPE.itemsize) == \
+    (80, 560, 64)
+
+
+class MultiTimeline(ctypes.Structure):   # mgenx_multi_timeline (a host struct)
+    _fields_ = [("t0_us", ctypes.c_int64), ("width_us", ctypes.c_uint64),
+                ("n_bins", ctypes.c_uint32), ("dev_bins", ctypes.c_void_p),
+                ("dev_outside", ctypes.c_void_p)]
+
+
 # ---- per-flow clock offset and skew (mgenx_flow_clock, include/mgenx.h) ----
 CLOCK_NONE = 0xFFFFFFFF     # MGENX_CLOCK_NONE
 CLOCK_OFFSET_ONLY = 0x1     # MGENX_CLOCK_OFFSET_ONLY

@@ -475,6 +475,47 @@ int mgenx_msg_match_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                              ctx->err, sizeof(ctx->err));
 }
 
+int mgenx_msg_match_multi(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                          const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                          const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len,
+                          uint32_t ns, const uint32_t* dev_recv_flow_idx,
+                          const uint32_t* dev_recv_seq, const uint32_t* dev_recv_tx_sec,
+                          const uint32_t* dev_recv_tx_usec, const uint32_t* dev_recv_rx_sec,
+                          const uint32_t* dev_recv_rx_usec, const uint32_t* dev_recv_rcv,
+                          uint32_t nr, uint32_t n_rcv, uint32_t n_flows, uint32_t opts,
+                          uint64_t* dev_send_mask, uint32_t* dev_recv_send,
+                          uint8_t* dev_recv_first, struct mgenx_rcv_cell* dev_cells,
+                          struct mgenx_flow_fanout* dev_fanout,
+                          struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
+                          void* stream) {
+  if (!ctx || !dev_stats || n_rcv < 1u || n_rcv > 64u || ns > (1u << 30) || nr > (1u << 30) ||
+      (uint64_t)n_flows * n_rcv >= (1ull << 31))
+    return MGENX_EINVAL;
+  if (ns && (!dev_send_flow_idx || !dev_send_seq || !dev_send_t_sec || !dev_send_t_usec ||
+             !dev_send_len || !dev_send_mask))
+    return MGENX_EINVAL;
+  if (nr && (!dev_recv_flow_idx || !dev_recv_seq || !dev_recv_tx_sec || !dev_recv_tx_usec ||
+             !dev_recv_rx_sec || !dev_recv_rx_usec || !dev_recv_rcv || !dev_recv_send ||
+             !dev_recv_first))
+    return MGENX_EINVAL;
+  if (n_flows && (!dev_cells || !dev_fanout)) return MGENX_EINVAL;
+  if (tl && tl->n_bins) {
+    const int64_t lim = (int64_t)1 << 62;
+    if (tl->width_us == 0 || tl->t0_us < -lim || tl->t0_us > lim ||
+        (uint64_t)n_flows * tl->n_bins >= (1ull << 31) ||
+        (n_flows && (!tl->dev_bins || !tl->dev_outside)))
+      return MGENX_EINVAL;
+  }
+  hipSetDevice(ctx->device);
+  return mgenx::msg_match_multi_run(ctx->match_ws, dev_send_flow_idx, dev_send_seq, dev_send_t_sec,
+                                   dev_send_t_usec, dev_send_len, ns, dev_recv_flow_idx,
+                                   dev_recv_seq, dev_recv_tx_sec, dev_recv_tx_usec,
+                                   dev_recv_rx_sec, dev_recv_rx_usec, dev_recv_rcv, nr, n_rcv,
+                                   n_flows, opts, dev_send_mask, dev_recv_send, dev_recv_first,
+                                   dev_cells, dev_fanout, dev_stats, tl, (hipStream_t)stream,
+                                   ctx->err, sizeof(ctx->err));
+}
+
 static int log_recv(mgenx_ctx* ctx, bool binary, const uint8_t* dev_slab, uint64_t slab_bytes,
                     const uint64_t* dev_rec_off, const uint32_t* dev_rec_len, uint64_t stride,
                     const mgenx_cols* cols,

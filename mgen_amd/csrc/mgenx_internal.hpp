@@ -111,7 +111,7 @@ struct mgenx_ctx {
   mgenx::DevBuf flowseries_ws;    // flow-series workspace (mgenx_flowseries.hip)
   mgenx::DevBuf flowquant_ws;     // windowed-percentile workspace (mgenx_flowquant.hip)
   mgenx::DevBuf flowclock_ws;     // clock offset / skew workspace (mgenx_flowclock.hip)
-  mgenx::DevBuf match_ws;         // msg-match workspace (mgenx_match.hip)
+  mgenx::DevBuf match_ws;         // msg-match workspace (mgenx_match.hip, mgenx_matchmulti.hip)
   mgenx::DevBuf tcp_ws;           // TCP transmit workspace (mgenx_pack_tcp)
   uint64_t* tcp_host = nullptr;   // host-mapped words: the plan's verdict (16 bytes)
   void* tcp_plan = nullptr;       // the plan's maximum word, skip word and look-back words
@@ -186,7 +186,7 @@ int flow_sort_run(void* mem, const uint32_t* flow_idx, uint32_t n, uint32_t n_fl
                   hipStream_t stream, char* err, size_t errn);
 
 // ---- mgenx_flowdist.hip, mgenx_flowseries.hip, mgenx_flowquant.hip, mgenx_flowclock.hip,
-// ---- mgenx_match.hip ----
+// ---- mgenx_match.hip, mgenx_matchmulti.hip ----
 int flow_dist_init_run(struct mgenx_flow_dist* dist, uint64_t* hist, uint32_t n_flows,
                        hipStream_t stream);
 // The passes mgenx_flow_dist and mgenx_flow_series share: the stable sort by flow (keys / order /
@@ -237,6 +237,17 @@ int msg_match_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_seq, con
                   uint32_t* recv_send, struct mgenx_flow_match* flows,
                   struct mgenx_match_stats* stats, const mgenx_match_timeline* tl,
                   hipStream_t stream, char* err, size_t errn);
+// mgenx_matchmulti.hip: ns, nr <= 2^30; 1 <= n_rcv <= 64; n_flows * n_rcv, n_flows * n_bins < 2^31
+int msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_seq,
+                        const uint32_t* s_sec, const uint32_t* s_usec, const uint32_t* s_len,
+                        uint32_t ns, const uint32_t* r_flow, const uint32_t* r_seq,
+                        const uint32_t* r_txs, const uint32_t* r_txu, const uint32_t* r_rxs,
+                        const uint32_t* r_rxu, const uint32_t* r_rcv, uint32_t nr, uint32_t n_rcv,
+                        uint32_t n_flows, uint32_t opts, uint64_t* send_mask, uint32_t* recv_send,
+                        uint8_t* recv_first, struct mgenx_rcv_cell* cells,
+                        struct mgenx_flow_fanout* fanout, struct mgenx_match_stats* stats,
+                        const mgenx_multi_timeline* tl, hipStream_t stream, char* err,
+                        size_t errn);
 
 // ---- mgenx_log.hip ----
 mgenx_log_ws* log_ws_new();

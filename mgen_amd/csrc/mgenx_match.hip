@@ -39,29 +39,23 @@
 //      match_runs_kernel<false>, match_run_base_kernel and match_runs_kernel<true> find each run
 //      where the main pass counts it, with its first and last U, count the listed ones per
 //      chunk, scan the counts and write the list in the order of the sorted positions.
+// The identity, the table with its build and mark kernels, the segmented sum and the carry
+// kernel are in mgenx_match.hpp, shared with mgenx_matchmulti.hip.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 #include <stdio.h>
 
-#include "mgenx_flowdist.hpp"
-#include "mgenx_internal.hpp"
+#include "mgenx_match.hpp"
 
 namespace mgenx {
 
 typedef struct mgenx_flow_match FlowMatch;
-typedef struct mgenx_match_stats MatchStats;
 static_assert(sizeof(FlowMatch) == 256, "mgenx_flow_match is 256 B");
-static_assert(sizeof(MatchStats) == 32, "mgenx_match_stats is 32 B");
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;      // an empty slot; MGENX_MATCH_NONE in the outputs
 constexpr uint32_t kFromFlowStart = 1u << 31;  // the segment began with its flow: no D yet
 constexpr uint32_t kLenMask = kFromFlowStart - 1u;
 enum : uint8_t { kX = 0, kU = 1, kD = 2 };
-
-struct MatchSide {  // the identity columns of one side
-  const uint32_t *flow, *seq, *sec, *usec;
-};
 
 // one sorted position as the main pass reads it
 struct alignas(16) MatchRec {
@@ -70,55 +64,6 @@ struct alignas(16) MatchRec {
   uint32_t rxc;  // D: send_rx_count
 };
 static_assert(sizeof(MatchRec) == 16, "MatchRec is 16 B");
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
-struct Ident {
-  uint32_t flow, seq, sec, usec;
-};
-__device__ __forceinline__ Ident ident_of(const MatchSide& s, uint32_t i, bool use_time) {
-  Ident d;
-  d.flow = s.flow[i];
-  d.seq = s.seq[i];
-  d.sec = use_time ? s.sec[i] : 0u;
-  d.usec = use_time ? s.usec[i] : 0u;
-  return d;
-}
-__device__ __forceinline__ bool ident_eq(const Ident& a, const Ident& b) {
-  return a.flow == b.flow && a.seq == b.seq && a.sec == b.sec && a.usec == b.usec;
-}
-__device__ __forceinline__ uint32_t ident_slot(const Ident& d, uint32_t mask) {
-  const uint64_t a = ((uint64_t)d.flow << 32) | d.seq, b = ((uint64_t)d.sec << 32) | d.usec;
-  return (uint32_t)mix64(mix64(a) ^ (b * 0x9E3779B97F4A7C15ull)) & mask;
-}
-
-// the slot's record index for identity `d`, or kEmpty (the table is complete: plain loads)
-__device__ __forceinline__ uint32_t table_find(const uint32_t* __restrict__ table, uint32_t mask,
-                                               const MatchSide& send, bool use_time,
-                                               const Ident& d) {
-  uint32_t slot = ident_slot(d, mask);
-  for (uint32_t k = 0; k <= mask; k++) {
-    const uint32_t v = table[slot];
-    if (v == kEmpty) return kEmpty;
-    if (ident_eq(ident_of(send, v, use_time), d)) return v;
-    slot = (slot + 1u) & mask;
-  }
-  return kEmpty;
-}
-
-// the sum of the lanes' counts of one wave, added by its first lane
-__device__ __forceinline__ void wave_count_add(uint64_t* dst, bool flag) {
-  const unsigned long long m = __ballot(flag);
-  if (m && (threadIdx.x & 63u) == 0u)
-    atomicAdd((unsigned long long*)dst, (unsigned long long)__popcll(m));
-}
 
 __global__ void match_init_kernel(FlowMatch* flows, uint32_t n_flows, MatchStats* stats,
                                   uint32_t* table, uint32_t n_slots) {
@@ -134,47 +79,6 @@ __global__ void match_init_kernel(FlowMatch* flows, uint32_t n_flows, MatchStats
     MatchStats s = {};
     *stats = s;
   }
-}
-
-__global__ void match_build_kernel(MatchSide send, uint32_t ns, uint32_t n_flows, bool use_time,
-                                   uint32_t* table, uint32_t mask, uint32_t* send_rx_count,
-                                   uint32_t* send_first_rx) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ns) return;
-  send_rx_count[i] = 0u;
-  send_first_rx[i] = kEmpty;
-  if (send.flow[i] >= n_flows) return;
-  const Ident me = ident_of(send, i, use_time);
-  uint32_t slot = ident_slot(me, mask);
-  // (at most ns identities in more than ns slots: an empty slot or the identity's own comes up)
-  for (uint32_t k = 0; k <= mask; k++) {
-    const uint32_t v = atomicCAS(&table[slot], kEmpty, i);
-    if (v == kEmpty) return;
-    if (ident_eq(ident_of(send, v, use_time), me)) {
-      if (i < v) atomicMin(&table[slot], i);
-      return;
-    }
-    slot = (slot + 1u) & mask;
-  }
-}
-
-__global__ void match_mark_kernel(MatchSide send, uint32_t ns, uint32_t n_flows, bool use_time,
-                                  const uint32_t* __restrict__ table, uint32_t mask,
-                                  uint32_t* __restrict__ own, MatchStats* stats) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool skipped = false, dup = false;
-  if (i < ns) {
-    uint32_t o = kEmpty;
-    if (send.flow[i] >= n_flows) {
-      skipped = true;
-    } else {
-      o = table_find(table, mask, send, use_time, ident_of(send, i, use_time));
-      dup = o != i;
-    }
-    own[i] = o;
-  }
-  wave_count_add(&stats->send_skipped, skipped);
-  wave_count_add(&stats->send_dup, dup);
 }
 
 __global__ void match_probe_kernel(MatchSide send, MatchSide recv, uint32_t nr, uint32_t n_flows,
@@ -214,59 +118,6 @@ __global__ void match_probe_kernel(MatchSide send, MatchSide recv, uint32_t nr, 
       atomicAdd((unsigned long long*)&flows[lf].rx_orphan, (unsigned long long)__popcll(same));
     left &= ~same;
   }
-}
-
-// ---- segmented inclusive sum over the kChunk lanes of a workgroup ----
-// `head` starts a segment at this lane.  Returns the sum of v over the lanes from the lane's
-// segment start (or lane 0) to the lane; *open = no segment starts at or before it.
-// s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
-struct SumOp {
-  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a + b; }
-};
-template <class Op>
-__device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t* s_v,
-                                                 uint32_t* s_h, bool* open) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t pv = __shfl_up(v, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      v = Op::of(pv, v);
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_v[w] = v;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    uint32_t wv = lane < kWaves ? s_v[lane] : 0u;
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const uint32_t pv = __shfl_up(wv, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        wv = Op::of(pv, wv);
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) {
-      s_v[lane] = wv;
-      s_h[lane] = wh;
-    }
-  }
-  __syncthreads();
-  if (w > 0 && !h) {
-    v = Op::of(s_v[w - 1], v);
-    h = s_h[w - 1];
-  }
-  *open = h == 0u;
-  __syncthreads();
-  return v;
 }
 
 // a position's word in the loss-run scan and whether it starts a segment
@@ -369,31 +220,6 @@ match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
   if (kTimeline) {
     const uint32_t fl = block_segsum<FlOp>(fl_word(cls, t), head, s_v, s_h, &open);
     if (t == last) trail_fl[c] = fl;
-  }
-}
-
-// pass 4b (one workgroup): carry[c] = the run word after chunk c's last position, over chunk c
-// and the chunks before it back to the last segment start
-__global__ void __launch_bounds__(kChunk)
-match_carry_kernel(const uint32_t* __restrict__ trail, const uint32_t* __restrict__ has_head,
-                   uint32_t n_chunks, uint32_t* __restrict__ carry) {
-  __shared__ uint32_t s_v[kWaves], s_h[kWaves];
-  __shared__ uint32_t s_run;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) s_run = 0u;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
-    const uint32_t c = base + t;
-    const bool in = c < n_chunks;
-    uint32_t v = in ? trail[c] : 0u;
-    const bool head = in ? has_head[c] != 0u : true;
-    bool open;
-    v = block_segsum<SumOp>(v, head, s_v, s_h, &open);
-    if (open) v += s_run;
-    if (in) carry[c] = v;
-    __syncthreads();  // every lane has read s_run
-    if (t == kChunk - 1u) s_run = v;
-    __syncthreads();
   }
 }
 
