@@ -19,7 +19,7 @@ HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \
        mgen_amd/csrc/mgenx_flowdist.hpp mgen_amd/csrc/mgenx_capture.hpp \
        mgen_amd/csrc/mgenx_flowquant.hpp mgen_amd/csrc/mgenx_flowclock.hpp \
-       mgen_amd/csrc/mgenx_match.hpp
+       mgen_amd/csrc/mgenx_match.hpp mgen_amd/csrc/mgenx_blockscan.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))
 DOBJ := $(addprefix build/diag/,$(addsuffix .o,$(NAMES)))
 LIBS := -L/opt/rocm/lib -lrccl -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib

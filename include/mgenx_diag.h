@@ -71,6 +71,25 @@ int mgenx_diag_worker_stamps(const mgenx_worker* w, uint32_t* out);
  * 512 words. */
 int mgenx_diag_chain_prof(unsigned long long* out);
 
+/* Diagnostic: the segmented inclusive scan of the per-flow passes (mgen_amd/csrc/
+ * mgenx_blockscan.hpp) alone: one workgroup of 1024 lanes, one scan.  dev_head: 1024 words, a
+ * non-zero word starts a segment at its lane.  dev_open: null (the scan is then asked for no
+ * open flags) or 1024 words that receive 1 where no segment starts at or before the lane.
+ *   kind 0: dev_val and dev_out 1024 x uint32_t, the sum modulo 2^32;
+ *   kind 1: dev_val and dev_out 1024 x int64_t, the maximum;
+ *   kind 2: dev_val 1024 x uint64_t, dev_out 1024 x 12 x uint64_t: lane t enters the 96-B value
+ *           whose field k = 0..11 is dev_val[t] * (2 k + 1) + k modulo 2^64; fields with
+ *           k % 3 == 0 are summed modulo 2^64, k % 3 == 1 take the minimum and k % 3 == 2 the
+ *           maximum, both as int64_t. */
+int mgenx_diag_blockscan(int kind, const void* dev_val, const uint32_t* dev_head, void* dev_out,
+                         uint32_t* dev_open, void* stream);
+/* Diagnostic: the same scan over n entries by one workgroup, 1024 entries a round, as the
+ * one-workgroup carry kernels run it.  dev_val, dev_head and dev_out hold n entries.
+ *   kind 0: uint32_t, the segmented sum modulo 2^32;  kind 1: int64_t, the segmented maximum;
+ *   kind 2: uint32_t, one sum over all entries (dev_head is not read and may be null). */
+int mgenx_diag_chunk_carry(int kind, const void* dev_val, const uint32_t* dev_head, uint32_t n,
+                           void* dev_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,7 +70,8 @@ EXPORTED_SYMBOLS = (
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
-                "mgenx_diag_chain_prof", "mgenx_diag_c1_giveups")
+                "mgenx_diag_chain_prof", "mgenx_diag_c1_giveups", "mgenx_diag_blockscan",
+                "mgenx_diag_chunk_carry")
 
 
 class MgenxError(RuntimeError):
@@ -155,6 +156,8 @@ def load(diag: bool = False):
         L.mgenx_diag_worker_stamps.argtypes = [P, P]
         L.mgenx_diag_chain_prof.argtypes = [P]
         L.mgenx_diag_c1_giveups.argtypes = [ctypes.POINTER(u64)]
+        L.mgenx_diag_blockscan.argtypes = [i32, P, P, P, P, P]
+        L.mgenx_diag_chunk_carry.argtypes = [i32, P, P, u32, P, P]
     L.mgenx_stream_scan.argtypes = [P, P, u64, i32, P, P, u64, ctypes.POINTER(ScanInfo), P]
     L.mgenx_tcp_rx_persist.argtypes = [P, P, P, P, u32, P, P, P, u32, P]
     L.mgenx_report_build.argtypes = [P, P, u32, u32, P, P, P, P, P, P, P]

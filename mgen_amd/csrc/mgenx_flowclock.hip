@@ -33,6 +33,7 @@
 #include <limits.h>
 #include <stdio.h>
 
+#include "mgenx_blockscan.hpp"
 #include "mgenx_flowclock.hpp"
 #include "mgenx_internal.hpp"
 
@@ -75,54 +76,40 @@ __device__ __forceinline__ bool clock_less(const ClockCand& a, const ClockCand& 
   if (a.d != b.d) return a.d < b.d;
   return a.p < b.p;
 }
+// the operators of the reductions (mgenx_blockscan.hpp's shape)
 struct ClockMinOp {
-  __device__ ClockCand operator()(const ClockCand& a, const ClockCand& b) const {
+  static __device__ ClockCand of(const ClockCand& a, const ClockCand& b) {
     return clock_less(b, a) ? b : a;
   }
 };
 struct ClockSumOp {
-  __device__ ClockSum operator()(const ClockSum& a, const ClockSum& b) const {
+  static __device__ ClockSum of(const ClockSum& a, const ClockSum& b) {
     const clock_u128 s = (((clock_u128)a.hi << 64) | a.lo) + (((clock_u128)b.hi << 64) | b.lo);
     return ClockSum{(uint64_t)s, (uint64_t)(s >> 64)};
   }
 };
 struct ClockResOp {
-  __device__ ClockRes operator()(const ClockRes& a, const ClockRes& b) const {
+  static __device__ ClockRes of(const ClockRes& a, const ClockRes& b) {
     return ClockRes{a.sum + b.sum, a.max > b.max ? a.max : b.max};
   }
 };
-
-template <class V>
-__device__ __forceinline__ V clock_shfl_xor(const V& v, int mask) {
-  static_assert(sizeof(V) % 4 == 0, "whole words");
-  constexpr int kW = sizeof(V) / 4;
-  union {
-    V v;
-    uint32_t w[kW];
-  } a, b;
-  a.v = v;
-#pragma unroll
-  for (int k = 0; k < kW; k++) b.w[k] = (uint32_t)__shfl_xor((int)a.w[k], mask);
-  return b.v;
-}
 
 constexpr uint32_t kClockSlotBytes = 40;  // the largest value reduced (ClockCand)
 
 // the reduction of v over the T lanes that serve a flow (a wave, or the whole workgroup), the
 // result in every lane.  T > 64: `slots` holds T / 64 values in LDS; all lanes of the workgroup
 // call this together.
-template <uint32_t T, class V, class Op>
-__device__ __forceinline__ V clock_reduce(V v, Op op, unsigned char* slots) {
+template <uint32_t T, class Op, class V>
+__device__ __forceinline__ V clock_reduce(V v, unsigned char* slots) {
   static_assert(sizeof(V) <= kClockSlotBytes, "a slot holds the value");
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = op(v, clock_shfl_xor(v, o));
+  v = wave_reduce<Op>(v);
   if constexpr (T > 64) {
     V* s = reinterpret_cast<V*>(slots);
     if ((threadIdx.x & 63u) == 0u) s[threadIdx.x >> 6] = v;
     __syncthreads();
     V r = s[0];
 #pragma unroll
-    for (uint32_t k = 1; k < T / 64u; k++) r = op(r, s[k]);
+    for (uint32_t k = 1; k < T / 64u; k++) r = Op::of(r, s[k]);
     __syncthreads();
     v = r;
   }
@@ -168,18 +155,18 @@ __device__ void clock_fit(const ClockPt* __restrict__ pt, const uint32_t* __rest
   ClockSum s = {0, 0};
   ClockCand l = clock_none(), r = clock_none(), low = clock_none();
   clock_each<T>(pt, b0, c, t, [&](const ClockPt& q, uint32_t p) {
-    s = ClockSumOp()(s, ClockSum{q.x, 0});
+    s = ClockSumOp::of(s, ClockSum{q.x, 0});
     const ClockCand cl = {0, 0, q.x, q.d, p, 0u};
     const ClockCand cr = {0, ~q.x, q.x, q.d, p, 0u};
     const ClockCand cd = {0, (uint64_t)q.d ^ kClockBias, q.x, q.d, p, 0u};
-    l = ClockMinOp()(l, cl);
-    r = ClockMinOp()(r, cr);
-    low = ClockMinOp()(low, cd);
+    l = ClockMinOp::of(l, cl);
+    r = ClockMinOp::of(r, cr);
+    low = ClockMinOp::of(low, cd);
   });
-  s = clock_reduce<T>(s, ClockSumOp(), slots);
-  l = clock_reduce<T>(l, ClockMinOp(), slots);
-  r = clock_reduce<T>(r, ClockMinOp(), slots);
-  low = clock_reduce<T>(low, ClockMinOp(), slots);
+  s = clock_reduce<T, ClockSumOp>(s, slots);
+  l = clock_reduce<T, ClockMinOp>(l, slots);
+  r = clock_reduce<T, ClockMinOp>(r, slots);
+  low = clock_reduce<T, ClockMinOp>(low, slots);
 
   // b. the edge over the mean
   bool found = true;
@@ -197,10 +184,10 @@ __device__ void clock_fit(const ClockPt* __restrict__ pt, const uint32_t* __rest
           const clock_i128 key = clock_key(l.x, l.d, r.x, r.d, q.x, q.d);
           const ClockCand cm = {(uint64_t)((clock_u128)key >> 64) ^ kClockBias, (uint64_t)key,
                                 q.x, q.d, p, 0u};
-          m = ClockMinOp()(m, cm);
+          m = ClockMinOp::of(m, cm);
         }
       });
-      m = clock_reduce<T>(m, ClockMinOp(), slots);
+      m = clock_reduce<T, ClockMinOp>(m, slots);
       if (m.k_hi >= kClockBias) {  // no point below the chord (none between its ends included)
         found = true;
         break;
@@ -216,9 +203,9 @@ __device__ void clock_fit(const ClockPt* __restrict__ pt, const uint32_t* __rest
   ClockRes res = {0, INT64_MIN};
   clock_each<T>(pt, b0, c, t, [&](const ClockPt& q, uint32_t) {
     const int64_t ci = clock_resid(xa, da, xb, db, q.x, q.d);
-    res = ClockResOp()(res, ClockRes{(uint64_t)ci, ci});
+    res = ClockResOp::of(res, ClockRes{(uint64_t)ci, ci});
   });
-  res = clock_reduce<T>(res, ClockResOp(), slots);
+  res = clock_reduce<T, ClockResOp>(res, slots);
   if (t == 0) {
     out->n = c;
     out->xa = xa;

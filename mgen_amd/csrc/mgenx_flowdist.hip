@@ -22,12 +22,14 @@
 //      or (shorter runs) atomics straight from the lanes.  Sums, minima and maxima of integers
 //      commute, so the bytes left do not depend on the order the workgroups finish in.
 // Passes 1 and 2 are mgenx::flow_prep_run, which mgenx_flow_series (mgenx_flowseries.hip) runs too;
-// what both main passes use of them (DistRec, block_segmax, kChunk) is in mgenx_flowdist.hpp.
+// what both main passes use of them is DistRec (mgenx_flowdist.hpp) and kChunk with the
+// segmented scan (mgenx_blockscan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 #include <stdio.h>
 
+#include "mgenx_blockscan.hpp"
 #include "mgenx_flowdist.hpp"
 #include "mgenx_internal.hpp"
 
@@ -162,11 +164,7 @@ flow_dist_tail_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restr
   // (the seq column, 4 B per record, stays in cache where the 32-B records do not: 80 against
   // 151 us at 8.4 M records)
   if (p <= pl && keys[p] == fl) v = (int64_t)seq[order[p]];
-#pragma unroll
-  for (uint32_t d = 32; d; d >>= 1) {
-    const int64_t o = __shfl_xor((long long)v, d);
-    v = v > o ? v : o;
-  }
+  v = wave_reduce<MaxOp>(v);
   if ((t & 63u) == 0u) s_v[t >> 6] = v;
   __syncthreads();
   if (t == 0) {
@@ -185,23 +183,13 @@ flow_dist_carry_kernel(const int64_t* __restrict__ tail_max, const uint32_t* __r
   __shared__ int64_t s_v[kWaves];
   __shared__ uint32_t s_h[kWaves];
   __shared__ int64_t s_run;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) s_run = kNone;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
-    const uint32_t c = base + t;
-    const bool in = c < n_chunks;
-    int64_t v = in ? tail_max[c] : kNone;
-    const bool head = in ? tail_cont[c] == 0u : true;
-    bool open;
-    v = block_segmax(v, head, s_v, s_h, &open);
-    const int64_t run = s_run;
-    if (open && run > v) v = run;
-    if (in) scan[c] = v;
-    __syncthreads();  // every lane has read s_run
-    if (t == kChunk - 1u) s_run = v;
-    __syncthreads();
-  }
+  chunk_carry<MaxOp>(
+      n_chunks, kNone,
+      [&](uint32_t c, int64_t& v) {
+        v = tail_max[c];
+        return tail_cont[c] == 0u;
+      },
+      [&](uint32_t c, int64_t v) { scan[c] = v; }, s_v, s_h, &s_run);
 }
 
 // pass 3: the statistics.  A lane per sorted position.
@@ -264,8 +252,7 @@ flow_dist_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restr
   }
   int64_t sv = active ? (int64_t)seq : kNone;
   if (base > sv) sv = base;
-  bool open;
-  const int64_t incl = block_segmax(sv, seg_head, s_v, s_h, &open);
+  const int64_t incl = seg_scan<MaxOp>(sv, seg_head, s_v, s_h);
   s_incl[t] = incl;
   __syncthreads();
 

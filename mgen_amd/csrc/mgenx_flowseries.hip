@@ -24,6 +24,7 @@
 #include <limits.h>
 #include <stdio.h>
 
+#include "mgenx_blockscan.hpp"
 #include "mgenx_flowdist.hpp"
 #include "mgenx_internal.hpp"
 
@@ -45,73 +46,24 @@ struct SeriesSnap {
   int64_t rsv;
 };
 
-// the terms of one record, or of a run of records of one (flow, bin)
+// the terms of one record, or of a run of records of one (flow, bin); its own operator for
+// seg_scan (mgenx_blockscan.hpp)
 struct SeriesAcc {
   uint64_t cnt;  // n | fresh << 16 | late << 32: at most kChunk each
   uint64_t bytes, lat_sum, jitter, advance;
   int64_t lat_min, lat_max;
+
+  static __device__ __forceinline__ SeriesAcc of(SeriesAcc a, const SeriesAcc& b) {
+    a.cnt += b.cnt;
+    a.bytes += b.bytes;
+    a.lat_sum += b.lat_sum;
+    a.jitter += b.jitter;
+    a.advance += b.advance;
+    a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
+    a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
+    return a;
+  }
 };
-
-__device__ __forceinline__ void acc_add(SeriesAcc& a, const SeriesAcc& b) {
-  a.cnt += b.cnt;
-  a.bytes += b.bytes;
-  a.lat_sum += b.lat_sum;
-  a.jitter += b.jitter;
-  a.advance += b.advance;
-  a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
-  a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
-}
-
-__device__ __forceinline__ SeriesAcc acc_shfl_up(const SeriesAcc& a, uint32_t d) {
-  SeriesAcc o;
-  o.cnt = __shfl_up((unsigned long long)a.cnt, d);
-  o.bytes = __shfl_up((unsigned long long)a.bytes, d);
-  o.lat_sum = __shfl_up((unsigned long long)a.lat_sum, d);
-  o.jitter = __shfl_up((unsigned long long)a.jitter, d);
-  o.advance = __shfl_up((unsigned long long)a.advance, d);
-  o.lat_min = __shfl_up((long long)a.lat_min, d);
-  o.lat_max = __shfl_up((long long)a.lat_max, d);
-  return o;
-}
-
-// ---- segmented inclusive scan of the terms over the kChunk lanes of a workgroup ----
-// `head` starts a run at this lane.  Leaves in `a` the terms combined over the lanes from the
-// lane's run start (or lane 0) to the lane.  s_a / s_h: kWaves entries each.
-__device__ __forceinline__ void block_segscan(SeriesAcc& a, bool head, SeriesAcc* s_a,
-                                              uint32_t* s_h) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const SeriesAcc pa = acc_shfl_up(a, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      acc_add(a, pa);
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_a[w] = a;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    SeriesAcc wa = s_a[lane < kWaves ? lane : 0u];
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const SeriesAcc pa = acc_shfl_up(wa, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        acc_add(wa, pa);
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) s_a[lane] = wa;
-  }
-  __syncthreads();
-  if (w > 0 && !h) acc_add(a, s_a[w - 1]);  // the run started in an earlier wave
-}
 
 __global__ void flow_series_init_kernel(SeriesState* state, SeriesBin* bins, uint32_t n_flows,
                                         uint32_t n_cells) {
@@ -201,8 +153,7 @@ flow_series_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __res
   }
   int64_t sv = active ? (int64_t)seq : kNone;
   if (base > sv) sv = base;
-  bool open;
-  const int64_t incl = block_segmax(sv, seg_head, s_v, s_h, &open);
+  const int64_t incl = seg_scan<MaxOp>(sv, seg_head, s_v, s_h);
   s_incl[t] = incl;
   __syncthreads();
 
@@ -243,7 +194,7 @@ flow_series_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __res
       d->seq_max = (uint32_t)incl;
     }
   }
-  block_segscan(a, run_head, s_a, s_h);
+  a = seg_scan<SeriesAcc, false>(a, run_head, s_a, s_h);
 
   if (active && run_tail) {
     const uint64_t n = a.cnt & 0xFFFFu;

@@ -1,10 +1,15 @@
 // mgenx_internal.hpp -- the host-side contract between the library's .hip files.
 //
-// Two headers are shared by the translation units, and each holds one kind of thing:
+// Three headers are shared by the translation units, and each holds one kind of thing:
 //   mgenx_kernels.hpp   what it takes to launch another file's kernel: the parameter blocks, the
 //                       launch_* functions, and the layouts host and device agree on (the
 //                       worker's mailbox, the report quantizer tables kRq*, the operator tables
 //                       kTab*).
+//   mgenx_blockscan.hpp device code only, for the per-flow passes (flow_dist, flow_series,
+//                       flow_clock, msg_match, msg_match_multi): the chunk size kChunk, word-wise
+//                       lane shuffles, the wave reduction, the segmented scan over a workgroup
+//                       and its carry over the chunks.  Included by the .hip files that use it,
+//                       not by this header.
 //   this header         host code only: device memory that grows on demand (DevBuf, Carve), the
 //                       context, and every host function that one file defines and another
 //                       calls.  Each is declared here once, in namespace mgenx, and both the

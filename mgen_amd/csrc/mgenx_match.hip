@@ -39,8 +39,8 @@
 //      match_runs_kernel<false>, match_run_base_kernel and match_runs_kernel<true> find each run
 //      where the main pass counts it, with its first and last U, count the listed ones per
 //      chunk, scan the counts and write the list in the order of the sorted positions.
-// The identity, the table with its build and mark kernels, the segmented sum and the carry
-// kernel are in mgenx_match.hpp, shared with mgenx_matchmulti.hip.
+// The identity, the table with its build and mark kernels and the carry kernel are in
+// mgenx_match.hpp, shared with mgenx_matchmulti.hip; the segmented scan is mgenx_blockscan.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
@@ -137,12 +137,6 @@ struct FlOp {
     return (ah > bh ? ah : bh) | (al > bl ? al : bl);
   }
 };
-struct MinOp {
-  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a < b ? a : b; }
-};
-struct MaxOp {
-  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a > b ? a : b; }
-};
 __device__ __forceinline__ uint32_t fl_word(uint8_t cls, uint32_t t) {
   return cls == kU ? ((0x800u - t) << 16) | (t + 1u) : 0u;
 }
@@ -209,8 +203,7 @@ match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     cls_out[p] = cls;
     v = run_word(cls, p == bnd[f], &head);
   }
-  bool open;
-  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
+  const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
   const int any = __syncthreads_or(active && head);
   const uint32_t last = (uint32_t)min((uint64_t)nv - p0, (uint64_t)kChunk) - 1u;
   if (t == last) {
@@ -218,84 +211,32 @@ match_pack_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     has_head[c] = any ? 1u : 0u;
   }
   if (kTimeline) {
-    const uint32_t fl = block_segsum<FlOp>(fl_word(cls, t), head, s_v, s_h, &open);
+    const uint32_t fl = seg_scan<FlOp>(fl_word(cls, t), head, s_v, s_h);
     if (t == last) trail_fl[c] = fl;
   }
 }
 
-// the terms of one position, or of a run of positions of one flow
+// the terms of one position, or of a run of positions of one flow; its own operator for seg_scan
 struct MatchAcc {
   uint64_t cnt;  // sent | send_dup << 16 | delivered << 32 | loss_runs << 48: at most kChunk each
   uint64_t sent_bytes, delivered_bytes, rx_dup, lat_sum, run_max;
   int64_t lat_min, lat_max;
   uint64_t hist[4];  // loss_run_hist[k] in bits 12 (k % 5) .. of word k / 5: at most kChunk each
+
+  static __device__ __forceinline__ MatchAcc of(MatchAcc a, const MatchAcc& b) {
+    a.cnt += b.cnt;
+    a.sent_bytes += b.sent_bytes;
+    a.delivered_bytes += b.delivered_bytes;
+    a.rx_dup += b.rx_dup;
+    a.lat_sum += b.lat_sum;
+    a.run_max = a.run_max > b.run_max ? a.run_max : b.run_max;
+    a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
+    a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
+#pragma unroll
+    for (int k = 0; k < 4; k++) a.hist[k] += b.hist[k];
+    return a;
+  }
 };
-
-__device__ __forceinline__ void acc_add(MatchAcc& a, const MatchAcc& b) {
-  a.cnt += b.cnt;
-  a.sent_bytes += b.sent_bytes;
-  a.delivered_bytes += b.delivered_bytes;
-  a.rx_dup += b.rx_dup;
-  a.lat_sum += b.lat_sum;
-  a.run_max = a.run_max > b.run_max ? a.run_max : b.run_max;
-  a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
-  a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
-#pragma unroll
-  for (int k = 0; k < 4; k++) a.hist[k] += b.hist[k];
-}
-
-__device__ __forceinline__ MatchAcc acc_shfl_up(const MatchAcc& a, uint32_t d) {
-  typedef unsigned long long ull;
-  MatchAcc o;
-  o.cnt = __shfl_up((ull)a.cnt, d);
-  o.sent_bytes = __shfl_up((ull)a.sent_bytes, d);
-  o.delivered_bytes = __shfl_up((ull)a.delivered_bytes, d);
-  o.rx_dup = __shfl_up((ull)a.rx_dup, d);
-  o.lat_sum = __shfl_up((ull)a.lat_sum, d);
-  o.run_max = __shfl_up((ull)a.run_max, d);
-  o.lat_min = __shfl_up((long long)a.lat_min, d);
-  o.lat_max = __shfl_up((long long)a.lat_max, d);
-#pragma unroll
-  for (int k = 0; k < 4; k++) o.hist[k] = __shfl_up((ull)a.hist[k], d);
-  return o;
-}
-
-// segmented inclusive scan of the terms over the kChunk lanes (mgenx_flowseries.hip's shape)
-__device__ __forceinline__ void block_segscan(MatchAcc& a, bool head, MatchAcc* s_a,
-                                              uint32_t* s_h) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const MatchAcc pa = acc_shfl_up(a, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      acc_add(a, pa);
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_a[w] = a;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    MatchAcc wa = s_a[lane < kWaves ? lane : 0u];
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const MatchAcc pa = acc_shfl_up(wa, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        acc_add(wa, pa);
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) s_a[lane] = wa;
-  }
-  __syncthreads();
-  if (w > 0 && !h) acc_add(a, s_a[w - 1]);  // the run started in an earlier wave
-}
 
 // pass 4c: the accounting.  A lane per sorted position.
 __global__ void __launch_bounds__(kChunk)
@@ -334,8 +275,7 @@ match_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     }
   }
   s_key[t] = f;
-  bool open;
-  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
+  const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
   s_incl[t] = incl;
   __syncthreads();
 
@@ -374,7 +314,7 @@ match_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     run_head = t == 0u || s_key[t - 1u] != f;
     run_tail = t == kChunk - 1u || s_key[t + 1u] != f;
   }
-  block_segscan(a, run_head, s_a, s_h);
+  a = seg_scan<MatchAcc, false>(a, run_head, s_a, s_h);
 
   if (active && run_tail) {
     FlowMatch* d = flows + f;
@@ -428,69 +368,24 @@ __global__ void match_tl_init_kernel(MatchBin* bins, uint32_t n_cells, uint64_t*
   if (i == 0 && n_runs) *n_runs = 0ull;
 }
 
-// the terms of one position, or of a run of positions of one (flow, window)
-struct SeriesAcc {
+// the terms of one position, or of a run of positions of one (flow, window); its own operator
+// for seg_scan
+struct MatchBinAcc {
   uint32_t cnt;  // sent | delivered << 16: at most kChunk each
   uint64_t sent_bytes, delivered_bytes, rx_dup, lat_sum;
   int64_t lat_min, lat_max;
+
+  static __device__ __forceinline__ MatchBinAcc of(MatchBinAcc a, const MatchBinAcc& b) {
+    a.cnt += b.cnt;
+    a.sent_bytes += b.sent_bytes;
+    a.delivered_bytes += b.delivered_bytes;
+    a.rx_dup += b.rx_dup;
+    a.lat_sum += b.lat_sum;
+    a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
+    a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
+    return a;
+  }
 };
-__device__ __forceinline__ void sacc_add(SeriesAcc& a, const SeriesAcc& b) {
-  a.cnt += b.cnt;
-  a.sent_bytes += b.sent_bytes;
-  a.delivered_bytes += b.delivered_bytes;
-  a.rx_dup += b.rx_dup;
-  a.lat_sum += b.lat_sum;
-  a.lat_min = a.lat_min < b.lat_min ? a.lat_min : b.lat_min;
-  a.lat_max = a.lat_max > b.lat_max ? a.lat_max : b.lat_max;
-}
-__device__ __forceinline__ SeriesAcc sacc_shfl_up(const SeriesAcc& a, uint32_t d) {
-  typedef unsigned long long ull;
-  SeriesAcc o;
-  o.cnt = __shfl_up(a.cnt, d);
-  o.sent_bytes = __shfl_up((ull)a.sent_bytes, d);
-  o.delivered_bytes = __shfl_up((ull)a.delivered_bytes, d);
-  o.rx_dup = __shfl_up((ull)a.rx_dup, d);
-  o.lat_sum = __shfl_up((ull)a.lat_sum, d);
-  o.lat_min = __shfl_up((long long)a.lat_min, d);
-  o.lat_max = __shfl_up((long long)a.lat_max, d);
-  return o;
-}
-// segmented inclusive scan of the terms over the kChunk lanes (block_segscan's shape)
-__device__ __forceinline__ void block_series_scan(SeriesAcc& a, bool head, SeriesAcc* s_a,
-                                                  uint32_t* s_h) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const SeriesAcc pa = sacc_shfl_up(a, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      sacc_add(a, pa);
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_a[w] = a;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    SeriesAcc wa = s_a[lane < kWaves ? lane : 0u];
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const SeriesAcc pa = sacc_shfl_up(wa, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        sacc_add(wa, pa);
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) s_a[lane] = wa;
-  }
-  __syncthreads();
-  if (w > 0 && !h) sacc_add(a, s_a[w - 1]);  // the run started in an earlier wave
-}
 
 // the series.  A lane per sorted position; the positions of one (flow, window) that follow each
 // other are reduced on chip and leave one atomic per field that is not its identity.  A cell
@@ -504,7 +399,7 @@ match_series_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restric
   typedef unsigned long long ull;
   __shared__ uint32_t s_key[kChunk];
   __shared__ uint32_t s_h[kWaves];
-  __shared__ SeriesAcc s_a[kWaves];
+  __shared__ MatchBinAcc s_a[kWaves];
 
   const uint32_t c = blockIdx.x, t = threadIdx.x;
   const uint32_t nv = bnd[n_flows];
@@ -514,7 +409,7 @@ match_series_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restric
   const bool active = p < nv;
 
   uint32_t key = kEmpty, f = 0u;
-  SeriesAcc a = {0u, 0, 0, 0, 0, INT64_MAX, INT64_MIN};
+  MatchBinAcc a = {0u, 0, 0, 0, 0, INT64_MAX, INT64_MIN};
   if (active) {
     f = keys[p];
     const uint8_t cls = cls_in[p];
@@ -540,7 +435,7 @@ match_series_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restric
   __syncthreads();
   const bool run_head = !active || t == 0u || s_key[t - 1u] != key;
   const bool run_tail = active && (t == kChunk - 1u || s_key[t + 1u] != key);
-  block_series_scan(a, run_head, s_a, s_h);
+  a = seg_scan<MatchBinAcc, false>(a, run_head, s_a, s_h);
 
   if (run_tail) {
     const uint32_t sent = a.cnt & 0xFFFFu, dlv = a.cnt >> 16;
@@ -571,35 +466,21 @@ match_carry_fl_kernel(const uint32_t* __restrict__ trail_fl, const uint32_t* __r
                       uint32_t* __restrict__ carry_last1) {
   __shared__ uint32_t s_v[kWaves], s_h[kWaves];
   __shared__ uint32_t s_first, s_last1;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    s_first = kEmpty;
-    s_last1 = 0u;
-  }
-  __syncthreads();
-  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
-    const uint32_t c = base + t;
-    const bool in = c < n_chunks;
-    const uint32_t w = in ? trail_fl[c] : 0u;
-    const bool head = in ? has_head[c] != 0u : true;
-    bool open;
-    uint32_t first = block_segsum<MinOp>(fl_first(w, c * kChunk), head, s_v, s_h, &open);
-    uint32_t last1 = block_segsum<MaxOp>(fl_last1(w, c * kChunk), head, s_v, s_h, &open);
-    if (open) {
-      first = MinOp::of(s_first, first);
-      last1 = MaxOp::of(s_last1, last1);
-    }
-    if (in) {
-      carry_first[c] = first;
-      carry_last1[c] = last1;
-    }
-    __syncthreads();  // every lane has read s_first / s_last1
-    if (t == kChunk - 1u) {
-      s_first = first;
-      s_last1 = last1;
-    }
-    __syncthreads();
-  }
+  // (two walks over the chunks, one word each: one walk of a two-word value would double s_v)
+  chunk_carry<MinOp>(
+      n_chunks, kEmpty,
+      [&](uint32_t c, uint32_t& v) {
+        v = fl_first(trail_fl[c], c * kChunk);
+        return has_head[c] != 0u;
+      },
+      [&](uint32_t c, uint32_t v) { carry_first[c] = v; }, s_v, s_h, &s_first);
+  chunk_carry<MaxOp>(
+      n_chunks, 0u,
+      [&](uint32_t c, uint32_t& v) {
+        v = fl_last1(trail_fl[c], c * kChunk);
+        return has_head[c] != 0u;
+      },
+      [&](uint32_t c, uint32_t v) { carry_last1[c] = v; }, s_v, s_h, &s_last1);
 }
 
 // the run list.  A run is found where match_main_kernel counts it: at the D that follows it or
@@ -655,9 +536,9 @@ match_runs_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
       if (cls != kD) v += s_cin[0];
     }
   }
-  bool open, open_fl;
-  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
-  const uint32_t fl = block_segsum<FlOp>(fl_word(cls, t), head, s_v, s_h, &open_fl) |
+  bool open_fl;
+  const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
+  const uint32_t fl = seg_scan<FlOp>(fl_word(cls, t), head, s_v, s_h, &open_fl) |
                       (open_fl ? 1u << 31 : 0u);  // bit 31: the segment began before the chunk
   s_incl[t] = incl;
   s_fl[t] = fl;
@@ -702,7 +583,7 @@ match_runs_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     if (t == 0u) chunk_n[c] = (uint32_t)n;
     return;
   }
-  const uint32_t rank1 = block_segsum<SumOp>(listed ? 1u : 0u, t == 0u, s_v, s_h, &open);
+  const uint32_t rank1 = seg_scan<SumOp>(listed ? 1u : 0u, t == 0u, s_v, s_h);
   if (listed) {
     const uint64_t at = (uint64_t)chunk_base[c] + rank1 - 1u;
     if (at < run_cap) {
@@ -727,20 +608,15 @@ match_run_base_kernel(const uint32_t* __restrict__ chunk_n, uint32_t n_chunks,
                       uint32_t* __restrict__ chunk_base, uint64_t* n_runs) {
   __shared__ uint32_t s_v[kWaves], s_h[kWaves];
   __shared__ uint32_t s_sum;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) s_sum = 0u;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
-    const uint32_t c = base + t;
-    const uint32_t n = c < n_chunks ? chunk_n[c] : 0u;
-    bool open;
-    const uint32_t incl = block_segsum<SumOp>(n, t == 0u, s_v, s_h, &open) + s_sum;
-    if (c < n_chunks) chunk_base[c] = incl - n;
-    __syncthreads();  // every lane has read s_sum
-    if (t == kChunk - 1u) s_sum = incl;
-    __syncthreads();
-  }
-  if (t == 0) *n_runs = s_sum;
+  uint32_t n = 0u;  // this lane's entry of the round
+  const uint32_t all = chunk_carry<SumOp>(
+      n_chunks, 0u,
+      [&](uint32_t c, uint32_t& v) {
+        v = n = chunk_n[c];
+        return false;  // one sum over all the chunks
+      },
+      [&](uint32_t c, uint32_t incl) { chunk_base[c] = incl - n; }, s_v, s_h, &s_sum);
+  if (threadIdx.x == 0) *n_runs = all;
 }
 
 // one lane per parsed line (mgenx_match_side; src_out may be src)

@@ -1,15 +1,15 @@
 // mgenx_match.hpp -- what the two joins share (mgenx_match.hip: one receiver; mgenx_matchmulti.hip:
 // many): the identity of a message, the open-addressing table of send indices with its build and
-// mark kernels, the per-wave counter add, and the segmented sum over a workgroup with the carry
-// over the chunks.  The kernels are `static`: each file that includes this header gets its own
-// copy in its own code object, launched from that file alone.
+// mark kernels, the per-wave counter add, and the carry of the loss-run word over the chunks (the
+// scan itself: mgenx_blockscan.hpp).  The kernels are `static`: each file that includes this
+// header gets its own copy in its own code object, launched from that file alone.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 
-#include "mgenx_flowdist.hpp"
+#include "mgenx_blockscan.hpp"
 #include "mgenx_internal.hpp"
 
 namespace mgenx {
@@ -118,59 +118,6 @@ static __global__ void match_mark_kernel(MatchSide send, uint32_t ns, uint32_t n
   wave_count_add(&stats->send_dup, dup);
 }
 
-// ---- segmented inclusive sum over the kChunk lanes of a workgroup ----
-// `head` starts a segment at this lane.  Returns the sum of v over the lanes from the lane's
-// segment start (or lane 0) to the lane; *open = no segment starts at or before it.
-// s_v / s_h: kWaves entries each.  Ends with every lane past the last barrier's reads.
-struct SumOp {
-  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a + b; }
-};
-template <class Op>
-__device__ __forceinline__ uint32_t block_segsum(uint32_t v, bool head, uint32_t* s_v,
-                                                 uint32_t* s_h, bool* open) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t h = head ? 1u : 0u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t pv = __shfl_up(v, d);
-    const uint32_t ph = __shfl_up(h, d);
-    if (lane >= d && !h) {
-      v = Op::of(pv, v);
-      h = ph;
-    }
-  }
-  if (lane == 63u) {
-    s_v[w] = v;
-    s_h[w] = h;
-  }
-  __syncthreads();
-  if (w == 0) {
-    uint32_t wv = lane < kWaves ? s_v[lane] : 0u;
-    uint32_t wh = lane < kWaves ? s_h[lane] : 1u;
-#pragma unroll
-    for (uint32_t d = 1; d < kWaves; d <<= 1) {
-      const uint32_t pv = __shfl_up(wv, d);
-      const uint32_t ph = __shfl_up(wh, d);
-      if (lane >= d && !wh) {
-        wv = Op::of(pv, wv);
-        wh = ph;
-      }
-    }
-    if (lane < kWaves) {
-      s_v[lane] = wv;
-      s_h[lane] = wh;
-    }
-  }
-  __syncthreads();
-  if (w > 0 && !h) {
-    v = Op::of(s_v[w - 1], v);
-    h = s_h[w - 1];
-  }
-  *open = h == 0u;
-  __syncthreads();
-  return v;
-}
-
 // (one workgroup) carry[c] = the summed word after chunk c's last position, over chunk c and the
 // chunks before it back to the last segment start.  trail[c]: the sum after chunk c's last
 // segment start; has_head[c]: the chunk has one.
@@ -179,22 +126,13 @@ match_carry_kernel(const uint32_t* __restrict__ trail, const uint32_t* __restric
                    uint32_t n_chunks, uint32_t* __restrict__ carry) {
   __shared__ uint32_t s_v[kWaves], s_h[kWaves];
   __shared__ uint32_t s_run;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) s_run = 0u;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_chunks; base += kChunk) {
-    const uint32_t c = base + t;
-    const bool in = c < n_chunks;
-    uint32_t v = in ? trail[c] : 0u;
-    const bool head = in ? has_head[c] != 0u : true;
-    bool open;
-    v = block_segsum<SumOp>(v, head, s_v, s_h, &open);
-    if (open) v += s_run;
-    if (in) carry[c] = v;
-    __syncthreads();  // every lane has read s_run
-    if (t == kChunk - 1u) s_run = v;
-    __syncthreads();
-  }
+  chunk_carry<SumOp>(
+      n_chunks, 0u,
+      [&](uint32_t c, uint32_t& v) {
+        v = trail[c];
+        return has_head[c] != 0u;
+      },
+      [&](uint32_t c, uint32_t v) { carry[c] = v; }, s_v, s_h, &s_run);
 }
 
 }  // namespace mgenx

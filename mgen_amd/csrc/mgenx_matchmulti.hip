@@ -48,50 +48,6 @@ constexpr uint32_t kCellRounds = 8;         // cells a wave combines before its 
 
 typedef unsigned long long ull;
 
-// sums and extremes over the 64 lanes of a wave; every lane calls, every lane gets the result
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor((ull)v, d);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t o = __shfl_xor(v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t o = __shfl_xor(v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const int64_t o = __shfl_xor((long long)v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const int64_t o = __shfl_xor((long long)v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // the (owner, rcv) table's first slot for a recv record of identity `d` at receiver r
 __device__ __forceinline__ uint32_t pair_slot(const Ident& d, uint32_t r, uint32_t mask) {
   const uint64_t a = ((uint64_t)d.flow << 32) | d.seq, b = ((uint64_t)d.sec << 32) | d.usec;
@@ -264,10 +220,10 @@ __global__ void multi_first_kernel(MatchSide send, MatchSide recv,
     uint64_t b = 0, ls = 0;
     int64_t lo = INT64_MAX, hi = INT64_MIN;
     if (n_first) {  // (the same in every lane)
-      b = wave_sum64(in ? bytes : 0ull);
-      ls = wave_sum64(in ? lat_u : 0ull);
-      lo = wave_min_i64(in ? lat_lo : INT64_MAX);
-      hi = wave_max_i64(in ? lat_hi : INT64_MIN);
+      b = wave_reduce<SumOp, uint64_t>(in ? bytes : 0ull);
+      ls = wave_reduce<SumOp, uint64_t>(in ? lat_u : 0ull);
+      lo = wave_reduce<MinOp, int64_t>(in ? lat_lo : INT64_MAX);
+      hi = wave_reduce<MaxOp, int64_t>(in ? lat_hi : INT64_MIN);
     }
     if (lane == lead) cell_add(cells + lk, n_first, n_dup, b, ls, lo, hi);
     left &= ~same;
@@ -303,8 +259,7 @@ multi_count_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict
     head = p == bnd[keys[p]];
     v = own[i] == i ? 1u : 0u;
   }
-  bool open;
-  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
+  const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
   const int any = __syncthreads_or(active && head);
   const uint32_t last = (uint32_t)min((uint64_t)nv - p0, (uint64_t)kChunk) - 1u;
   if (t == last) {
@@ -344,8 +299,7 @@ multi_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     // the chunk's first position inside a flow continues the chunks before it (c > 0)
     if (t == 0u && !head) v += carry[c - 1u];
   }
-  bool open;
-  const uint32_t incl = block_segsum<SumOp>(v, head, s_v, s_h, &open);
+  const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
   // the owner's rank among its flow's owners, and the word the cells keep
   const uint64_t pk = ((uint64_t)(incl - (owner ? 1u : 0u)) << 32) | i;
   const uint32_t pc = (uint32_t)__popcll(m);
@@ -363,8 +317,8 @@ multi_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
     FlowFanout* d = fanout + lf;
     if (lane == lead && dup) atomicAdd((ull*)&d->send_dup, (ull)dup);
     if (sent) {  // (the same in every lane, as every branch on a ballot below)
-      const uint64_t bytes = wave_sum64(ow ? (uint64_t)ln : 0ull);
-      const uint32_t deliv = wave_sum32(ow ? pc : 0u);
+      const uint64_t bytes = wave_reduce<SumOp, uint64_t>(ow ? ln : 0u);
+      const uint32_t deliv = wave_reduce<SumOp, uint32_t>(ow ? pc : 0u);
       const uint32_t all = (uint32_t)__popcll(__ballot(ow && pc == n_rcv));
       // reach_hist[k], k < n_rcv: lane k keeps the count (no array indexed at run time)
       uint32_t hc = 0u;
@@ -443,13 +397,13 @@ multi_series_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restric
     if (lk & kOutsideKey) {
       if (lane == lead) atomicAdd((ull*)&outside[lk & ~kOutsideKey], (ull)sent);
     } else {
-      const uint64_t bytes = wave_sum64(in ? (uint64_t)ln : 0ull);
-      const uint32_t deliv = wave_sum32(in ? pc : 0u);
-      const uint64_t dbytes = wave_sum64(in ? (uint64_t)ln * pc : 0ull);
+      const uint64_t bytes = wave_reduce<SumOp, uint64_t>(in ? ln : 0u);
+      const uint32_t deliv = wave_reduce<SumOp, uint32_t>(in ? pc : 0u);
+      const uint64_t dbytes = wave_reduce<SumOp, uint64_t>(in ? (uint64_t)ln * pc : 0ull);
       const uint32_t any = (uint32_t)__popcll(__ballot(in && pc > 0u));
       const uint32_t all = (uint32_t)__popcll(__ballot(in && pc == n_rcv));
-      const uint32_t lo = wave_min32(in ? pc : 0xFFFFFFFFu);
-      const uint32_t hi = wave_max32(in ? pc : 0u);
+      const uint32_t lo = wave_reduce<MinOp, uint32_t>(in ? pc : 0xFFFFFFFFu);
+      const uint32_t hi = wave_reduce<MaxOp, uint32_t>(in ? pc : 0u);
       if (lane == lead) {
         MultiBin* d = bins + lk;
         atomicAdd((ull*)&d->sent, (ull)sent);

@@ -1,8 +1,12 @@
 // mgenx_probe.hip -- memory-pattern probes of the diagnostics build (mgenx_diag_stream_read*,
-// mgenx_diag_group_rw): no unpack code, and nothing at all in the product library.
+// mgenx_diag_group_rw) and the probes of the per-flow passes' scan (mgenx_diag_blockscan,
+// mgenx_diag_chunk_carry): no unpack code, and nothing at all in the product library.
 #include "mgenx_internal.hpp"
 
 #if MGENX_DIAG
+#include "mgenx_blockscan.hpp"
+#include "mgenx_diag.h"
+
 namespace mgenx {
 
 // Diagnostic: streaming read of `bytes` (16 B per lane per load, grid-stride), XOR-folded
@@ -256,5 +260,102 @@ hipError_t launch_stream_read(const uint8_t* p, uint64_t bytes, uint32_t* out, i
   return hipGetLastError();
 }
 
+// Diagnostic: mgenx_blockscan.hpp's scan and carry loop alone, one workgroup
+// (mgenx_diag_blockscan, mgenx_diag_chunk_carry; include/mgenx_diag.h).
+struct ScanProbe {  // the widest value in use (mgenx_match.hip's MatchAcc): 96 B
+  uint64_t f[12];   // field k: k % 3 == 0 a wrapping sum, 1 a signed minimum, 2 a signed maximum
+  static __device__ __forceinline__ ScanProbe of(ScanProbe a, const ScanProbe& b) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+      const int64_t x = (int64_t)a.f[k], y = (int64_t)b.f[k];
+      const uint64_t m = k % 3 == 1 ? (x < y ? x : y) : (x > y ? x : y);
+      a.f[k] = k % 3 == 0 ? a.f[k] + b.f[k] : m;
+    }
+    return a;
+  }
+};
+__device__ __forceinline__ uint32_t scan_probe_value(uint32_t in, uint32_t*) { return in; }
+__device__ __forceinline__ int64_t scan_probe_value(int64_t in, int64_t*) { return in; }
+__device__ __forceinline__ ScanProbe scan_probe_value(uint64_t in, ScanProbe*) {
+  ScanProbe v;
+#pragma unroll
+  for (int k = 0; k < 12; k++) v.f[k] = in * (uint64_t)(2 * k + 1) + (uint64_t)k;
+  return v;
+}
+
+// one kernel per kind and per use of `open`, as the callers compile the scan: the 96-B value
+// keeps its registers to itself
+template <class Op, bool kSync, bool kOpen, class In, class V>
+__global__ void __launch_bounds__(kChunk)
+blockscan_probe_kernel(const In* val, const uint32_t* head, V* out, uint32_t* open_out) {
+  __shared__ V s_v[kWaves];
+  __shared__ uint32_t s_h[kWaves];
+  const uint32_t t = threadIdx.x;
+  const V v = scan_probe_value(val[t], (V*)nullptr);
+  bool open = false;
+  out[t] = seg_scan<Op, kSync>(v, head[t] != 0u, s_v, s_h, kOpen ? &open : nullptr);
+  if (kOpen) open_out[t] = open ? 1u : 0u;
+}
+template <class Op, bool kSync, class In, class V>
+hipError_t launch_blockscan_probe(const void* val, const uint32_t* head, void* out,
+                                  uint32_t* open_out, hipStream_t stream) {
+  if (open_out)
+    hipLaunchKernelGGL((blockscan_probe_kernel<Op, kSync, true, In, V>), dim3(1), dim3(kChunk), 0,
+                       stream, (const In*)val, head, (V*)out, open_out);
+  else
+    hipLaunchKernelGGL((blockscan_probe_kernel<Op, kSync, false, In, V>), dim3(1), dim3(kChunk), 0,
+                       stream, (const In*)val, head, (V*)out, open_out);
+  return hipGetLastError();
+}
+
+template <class Op, class V>
+__device__ __forceinline__ void carry_probe(const V* val, const uint32_t* head, uint32_t n, V idle,
+                                            V* out) {
+  __shared__ V s_v[kWaves];
+  __shared__ uint32_t s_h[kWaves];
+  __shared__ V s_run;
+  chunk_carry<Op>(
+      n, idle,
+      [&](uint32_t c, V& v) {
+        v = val[c];
+        return head && head[c] != 0u;
+      },
+      [&](uint32_t c, V v) { out[c] = v; }, s_v, s_h, &s_run);
+}
+
+__global__ void __launch_bounds__(kChunk)
+chunk_carry_probe_kernel(int kind, const void* val, const uint32_t* head, uint32_t n, void* out) {
+  if (kind == 0)
+    carry_probe<SumOp>((const uint32_t*)val, head, n, 0u, (uint32_t*)out);
+  else if (kind == 1)
+    carry_probe<MaxOp>((const int64_t*)val, head, n, (int64_t)INT64_MIN, (int64_t*)out);
+  else
+    carry_probe<SumOp>((const uint32_t*)val, (const uint32_t*)nullptr, n, 0u, (uint32_t*)out);
+}
+
 }  // namespace mgenx
+
+extern "C" int mgenx_diag_blockscan(int kind, const void* dev_val, const uint32_t* dev_head,
+                                    void* dev_out, uint32_t* dev_open, void* stream) {
+  if (kind < 0 || kind > 2 || !dev_val || !dev_head || !dev_out) return MGENX_EINVAL;
+  using namespace mgenx;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e =
+      kind == 0 ? launch_blockscan_probe<SumOp, true, uint32_t, uint32_t>(dev_val, dev_head,
+                                                                          dev_out, dev_open, s)
+      : kind == 1 ? launch_blockscan_probe<MaxOp, true, int64_t, int64_t>(dev_val, dev_head,
+                                                                          dev_out, dev_open, s)
+                  : launch_blockscan_probe<ScanProbe, false, uint64_t, ScanProbe>(
+                        dev_val, dev_head, dev_out, dev_open, s);
+  return e == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
+}
+
+extern "C" int mgenx_diag_chunk_carry(int kind, const void* dev_val, const uint32_t* dev_head,
+                                      uint32_t n, void* dev_out, void* stream) {
+  if (kind < 0 || kind > 2 || (n && (!dev_val || !dev_out || (kind != 2 && !dev_head))))
+    return MGENX_EINVAL;
+  hipLaunchKernelGGL(mgenx::chunk_carry_probe_kernel, dim3(1), dim3(mgenx::kChunk), 0,
+                     (hipStream_t)stream, kind, dev_val, dev_head, n, dev_out);
+  return hipGetLastError() == hipSuccess ? MGENX_OK : MGENX_EDEVICE;
+}
 #endif  // MGENX_DIAG

@@ -86,6 +86,21 @@ def test_one_long_flow_carries_its_maximum_across_chunks(torch, eng, data):
     check(run(torch, eng, nf, fi, c), want)
 
 
+def test_maximum_carried_past_the_carry_kernels_first_round(torch, eng):
+    """One flow of 2^20 + 1025 + 3 records (1026 chunks: flow_dist_carry_kernel walks a second
+    round of 1024 chunks with the flow still open).  The largest seq is at input position 0 and
+    the later ones rise below it, so a maximum that is not carried leaves a record unreordered.
+    The expectation is closed-form; the model (vectorised over one flow) checks the rest."""
+    n = 2**20 + 1025 + 3
+    seq = np.concatenate([[n - 1], np.arange(n - 1)])
+    nf, fi, c = (1,) + R._synth(np.zeros(n, np.int64), seq, 23)
+    d, h = run(torch, eng, nf, fi, c)
+    assert int(d[0]["n"]) == n and int(d[0]["reordered"]) == n - 1
+    assert (int(d[0]["seq_min"]), int(d[0]["seq_max"])) == (0, n - 1)
+    assert int(d[0]["reorder_max"]) == n - 1 and int(d[0]["reorder_sum"]) == n * (n - 1) // 2
+    check((d, h), R.model(nf, fi, c))
+
+
 def test_flow_edges_at_every_chunk_offset(torch, eng):
     nf, fi, c = R.boundary_sweep()
     assert len(fi) == 80_200

@@ -193,6 +193,36 @@ def test_many_short_runs_and_one_delivered(torch, eng):
     assert int(flows[1]["delivered"]) == 1 and int(flows[1]["loss_runs"]) == 2
 
 
+def test_one_run_past_the_carry_kernels_first_round(torch, eng):
+    """One flow of 2^20 + 1025 + 3 messages of which only the first and the last arrive: 1026
+    chunks, so the one-workgroup carry kernels (match_carry_kernel; for the run list also
+    match_carry_fl_kernel and match_run_base_kernel) walk a second round of 1024 chunks with the
+    run still open.  The expectation is closed-form."""
+    from mgen_amd import LOSS_RUN_DTYPE
+    ns = 2**20 + 1025 + 3
+    send, _ = make(np.zeros(ns), np.arange(ns))
+    recv = recv_of(send, [0, ns - 1])
+    cnt, first, rs, flows, stats = run(torch, eng, 1, send, recv)
+    f = flows[0]
+    assert rs.tolist() == [0, ns - 1] and int(cnt.sum()) == 2
+    assert (int(f["sent"]), int(f["delivered"])) == (ns, 2)
+    assert (int(f["loss_runs"]), int(f["loss_run_max"])) == (1, ns - 2)
+    want_hist = [0] * 18
+    want_hist[min((ns - 2).bit_length() - 1, 17)] = 1
+    assert f["loss_run_hist"].tolist() == want_hist
+    assert int(f["lost_head"]) == 0 == int(f["lost_tail"])
+    # the run list at min_run = 1
+    out = eng.msg_match_timeline(1, {k: dev(torch, v) for k, v in send.items()},
+                                 {k: dev(torch, v) for k, v in recv.items()},
+                                 T0 * 10**6, 2**40, 1, min_run=1)
+    torch.cuda.synchronize()
+    assert out[3].cpu().numpy().tobytes() == flows.tobytes()
+    runs = out[7].cpu().numpy().view(LOSS_RUN_DTYPE)
+    assert len(runs) == 1
+    assert (int(runs[0]["flow_idx"]), int(runs[0]["length"])) == (0, ns - 2)
+    assert (int(runs[0]["first_send"]), int(runs[0]["last_send"])) == (1, ns - 2)
+
+
 # ------------------------------------------------------------------ identity and duplicates
 def test_identity(torch, eng):
     """Equal (flow, seq) with different stamps: distinct messages, duplicates under NO_TIME.
