@@ -11,7 +11,7 @@ NAMES := mgenx_api mgenx_ctx mgenx_unpack mgenx_unpack_fixed mgenx_probe \
          mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_binlog mgenx_comm mgenx_worker \
          mgenx_worker_host mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse \
          mgenx_flowdist mgenx_defrag mgenx_pcap_tcp mgenx_flowseries mgenx_match \
-         mgenx_flowquant mgenx_flowclock mgenx_matchmulti
+         mgenx_flowquant mgenx_flowclock mgenx_matchmulti mgenx_binlogparse
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_internal.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
@@ -19,7 +19,8 @@ HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_
        mgen_amd/csrc/mgenx_parse.hpp mgen_amd/csrc/mgenx_logparse.hpp mgen_amd/csrc/mgenx_pcapng.hpp \
        mgen_amd/csrc/mgenx_flowdist.hpp mgen_amd/csrc/mgenx_capture.hpp \
        mgen_amd/csrc/mgenx_flowquant.hpp mgen_amd/csrc/mgenx_flowclock.hpp \
-       mgen_amd/csrc/mgenx_match.hpp mgen_amd/csrc/mgenx_blockscan.hpp
+       mgen_amd/csrc/mgenx_match.hpp mgen_amd/csrc/mgenx_blockscan.hpp \
+       mgen_amd/csrc/mgenx_binlogparse.hpp
 OBJ := $(addprefix build/product/,$(addsuffix .o,$(NAMES)))
 DOBJ := $(addprefix build/diag/,$(addsuffix .o,$(NAMES)))
 LIBS := -L/opt/rocm/lib -lrccl -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
@@ -30,7 +31,7 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
      tests/cpp/flow_series_host tests/cpp/msg_match_host tests/cpp/flow_quant_host \
      tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host \
-     tests/cpp/match_timeline_host tests/cpp/msg_match_multi_host
+     tests/cpp/match_timeline_host tests/cpp/msg_match_multi_host tests/cpp/binlog_parse_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -91,6 +92,13 @@ tools/pcap2mgen: tools/pcap2mgen.cpp include/mgenx_pcap.hpp include/mgenx.hpp in
 # the text log line parser (mgenx_logparse.hpp) as a stand-alone host program under the address
 # and undefined-behaviour sanitizers (tests/test_logparse_cpu.py); no HIP, no GPU
 tests/cpp/logparse_host: tests/cpp/logparse_host.cpp mgen_amd/csrc/mgenx_logparse.hpp include/mgenx.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Iinclude $< -o $@
+
+# the binary log record decoder and the record walk's stop rule (mgenx_binlogparse.hpp) as a
+# stand-alone host program under the address and undefined-behaviour sanitizers
+# (tests/test_binlog_parse_cpu.py); no HIP, no GPU
+tests/cpp/binlog_parse_host: tests/cpp/binlog_parse_host.cpp mgen_amd/csrc/mgenx_binlogparse.hpp include/mgenx.h
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Iinclude $< -o $@
 

@@ -1449,6 +1449,47 @@ int mgenx_log_parse_text(mgenx_ctx* ctx, const char* dev_text, uint64_t nbytes,
                          const uint64_t* dev_line_off, uint32_t n, uint32_t opts,
                          uint32_t day_base_sec, const mgenx_logparse_out* out, void* stream);
 
+/* ---- binary log ingest: MGEN binary log records -> the same columns ----
+ * mgenx_binlog_header (HOST memory, no device work) applies the header-line rules of
+ * mgenx_binlog_index and nothing else: status MGENX_BINLOG_OK or _HEADER, version, and
+ * consumed = the offset of the first record (n_records stays 0).
+ *
+ * mgenx_binlog_parse: n records at dev_rec_off (what mgenx_binlog_index found) -> one element
+ * per record in every array of `out` that is given, with the optional-pointer rules and the
+ * two-pass payload / payload_cap / payload_off convention of mgenx_log_parse_text.  opts must be
+ * 0.  For record i the outputs are what mgenx_log_parse_text gives for that record's own line
+ * in mgenx_convert_binary_log(flags 0, opts MGENX_LOG_EPOCH) -- the REPORT lines that MGEN_DATA
+ * items add are not records and have no element -- except, decided from the record's bytes:
+ *   ttl        -1 and MGENX_HAS_TTL clear, always: the record holds no TTL (the converter's
+ *              ttl> value is its log_flush flag, mgenMsg.cpp:1607).
+ *   rejected   a RECV / SEND record whose stored message Unpack rejects (shorter than 28 bytes,
+ *              version not 2, unknown destination type) has event set, status
+ *              MGENX_PARSE_MALFORMED and its other outputs unspecified (the converter logs a
+ *              fresh MgenMsg's members there).
+ *   values the text grammar refuses (tx_usec or an event's usec >= 10^6 ...) are kept as they
+ *              are, status OK.
+ *   SEND       rx_sec / rx_usec = the stored message's tx time (the record has no event time,
+ *              mgenMsg.cpp:1152-1209; it is the converted line's stamp too); src all zero (type
+ *              0, port 0: the record has no source port); size = the stored mgen_msg_len word
+ *              for a TCP SEND, the header's msg_len otherwise; cols.tx_sec / tx_usec 0.
+ *   others     LISTEN ... RECONNECT and START / STOP: event, the stamp, status OK, cols.err
+ *              MGENX_ERROR_NOT_RECV, protocol 0, the rest 0 (ttl -1).
+ *   cols.err   0 for an OK RECV record only (a binary log never holds RERR).
+ * Where the text route agrees, so does this one: a source, destination or host address whose
+ * length does not fit its type (the converter prints "(invalid)") is MGENX_PARSE_MALFORMED; a
+ * RECV whose GPS status is unknown has no GPS, data or flags (LogRecvEvent ends the line
+ * there); cols.flags holds the CONTINUES / END_OF_MSG / CHECKSUM_ERROR bits only; the data>
+ * bytes start at the word-floored end of the message header (payload_data) and are there for
+ * payload type 0 only; a message too short for its GPS fields reads INVALID,0,0,0.
+ * A record the index would have stopped at (short for its type, RERR, unknown event, cut by
+ * buf_bytes) is MGENX_PARSE_MALFORMED: no read leaves [rec_off[i], rec_off[i] + 4 +
+ * recordLength) nor buf_bytes.  Asynchronous; n == 0 is legal; with payload_off the context
+ * keeps a workspace (16 bytes per record), shared with mgenx_log_parse_text. */
+int mgenx_binlog_header(const uint8_t* buf, uint64_t nbytes, mgenx_binlog_info* info);
+int mgenx_binlog_parse(mgenx_ctx* ctx, const uint8_t* dev_buf, uint64_t buf_bytes,
+                       const uint64_t* dev_rec_off, uint32_t n, uint32_t opts,
+                       const mgenx_logparse_out* out, void* stream);
+
 /* ---- a sender's log joined with a receiver's log: per-message loss ----
  * A sender logging SEND lines (TXLOG) and a receiver logging RECV lines is the manual's basic
  * workflow.  On the UDP and TCP paths the SEND line carries the message's own tx_time

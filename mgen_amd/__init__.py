@@ -33,6 +33,7 @@ from ._abi import (  # noqa: F401
     PCAP_TCP, TCP_SYN, TCP_GAP, TCP_STREAM_DTYPE, TcpStats,
     MATCH_NONE, MATCH_NO_TIME, MATCH_RUN_BINS, FLOW_MATCH_DTYPE, MATCH_STATS_DTYPE,
     RUN_HEAD, RUN_TAIL, MATCH_BIN_DTYPE, LOSS_RUN_DTYPE, MatchTimeline,
+    BINLOG_OK, BINLOG_HEADER, BINLOG_TOO_LONG, BINLOG_EVENT, BINLOG_SHORT,
     CLOCK_NONE, CLOCK_OFFSET_ONLY, FLOW_CLOCK_DTYPE,
     MATCH_MAX_RCV, RCV_CELL_DTYPE, FLOW_FANOUT_DTYPE, MULTI_BIN_DTYPE, MultiTimeline,
 )
@@ -66,7 +67,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcap_defrag", "mgenx_pcapng_defrag",
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
     "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock", "mgenx_msg_match_ex",
-    "mgenx_msg_match_multi",
+    "mgenx_msg_match_multi", "mgenx_binlog_header", "mgenx_binlog_parse",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -144,6 +145,8 @@ def load(diag: bool = False):
                                   u64, P, ctypes.POINTER(u64), P]
     L.mgenx_binlog_index.argtypes = [P, u64, P, u64, ctypes.POINTER(BinlogInfo)]
     L.mgenx_convert_binary_log.argtypes = [P, P, u64, P, u32, u32, u32, P, u64, P, P]
+    L.mgenx_binlog_header.argtypes = [P, u64, ctypes.POINTER(BinlogInfo)]
+    L.mgenx_binlog_parse.argtypes = [P, P, u64, P, u32, u32, ctypes.POINTER(LogparseOut), P]
     L.mgenx_text_index.argtypes = [P, P, u64, P, u64, P, P]
     L.mgenx_log_parse_text.argtypes = [P, P, u64, P, u32, u32, u32, ctypes.POINTER(LogparseOut),
                                        P]
@@ -395,9 +398,32 @@ class Engine:
         tensors: event, status, protocol, present, rx_sec, rx_usec, src (n x 20), ttl, size,
         the mgenx_cols columns (core + extended, ready for flow_lookup / flow_reduce) and, with
         payload=True, payload (the decoded data> bytes) and payload_off (n + 1)."""
+        nbytes = text.numel() if nbytes is None else nbytes
+
+        def call(s):
+            rc = self.lib.mgenx_log_parse_text(self.ctx, _ptr(text), nbytes, _ptr(line_off), n,
+                                               opts, day_base, ctypes.byref(s),
+                                               _stream(self.device))
+            self._check(rc, "mgenx_log_parse_text")
+        return self._logparse_out(n, payload, call)
+
+    def binlog_parse(self, buf, rec_off, n, *, payload=False, nbytes=None):
+        """Parse n binary log records into columns (mgenx_binlog_parse): buf is the log image
+        (uint8 tensor), rec_off the record offsets (int64 tensor, from binlog_index).  Returns
+        the same dict of tensors as log_parse_text, one element per record."""
+        nbytes = buf.numel() if nbytes is None else nbytes
+
+        def call(s):
+            rc = self.lib.mgenx_binlog_parse(self.ctx, _ptr(buf), nbytes, _ptr(rec_off), n, 0,
+                                             ctypes.byref(s), _stream(self.device))
+            self._check(rc, "mgenx_binlog_parse")
+        return self._logparse_out(n, payload, call)
+
+    def _logparse_out(self, n, payload, call):
+        """The output tensors of a mgenx_logparse_out, filled by call(struct) (twice when the
+        payload bytes did not fit the first time)."""
         torch = self.torch
         dev = f"cuda:{self.device}"
-        nbytes = text.numel() if nbytes is None else nbytes
         m = max(n, 1)
         out = {name: torch.zeros(m * w, dtype=getattr(torch, dt), device=dev)
                for name, dt, w in LOGPARSE_COLS}
@@ -415,10 +441,7 @@ class Engine:
             if payload:
                 out["payload"] = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
                 s.payload, s.payload_cap = out["payload"].data_ptr(), cap
-            rc = self.lib.mgenx_log_parse_text(self.ctx, _ptr(text), nbytes, _ptr(line_off), n,
-                                               opts, day_base, ctypes.byref(s),
-                                               _stream(self.device))
-            self._check(rc, "mgenx_log_parse_text")
+            call(s)
             if not payload:
                 break
             total = int(out["payload_off"][n].item())
@@ -1341,6 +1364,59 @@ def binlog_index(buf) -> tuple:
     return offs[:int(info.n_records)], info
 
 
+def binlog_header(buf) -> BinlogInfo:
+    """mgenx_binlog_header over a host log image: the header-line rules of binlog_index alone.
+    status is BINLOG_OK for a binary log (consumed = the offset of its first record), else
+    BINLOG_HEADER."""
+    L = load()
+    b = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+    info = BinlogInfo()
+    if b.size == 0:
+        info.status = BINLOG_HEADER
+        return info
+    if L.mgenx_binlog_header(b.ctypes.data_as(ctypes.c_void_p), b.size, ctypes.byref(info)) != 0:
+        raise MgenxError("mgenx_binlog_header failed")
+    return info
+
+
+def is_binary_log(buf) -> bool:
+    """True when buf starts with the header line of an MGEN binary log."""
+    return binlog_header(buf).status == BINLOG_OK
+
+
+_BINLOG_STATUS = {BINLOG_HEADER: "HEADER", BINLOG_TOO_LONG: "TOO_LONG", BINLOG_EVENT: "EVENT",
+                  BINLOG_SHORT: "SHORT"}
+
+
+def _ingest_log(eng, log_bytes, day_base):
+    """A log image -> (parsed columns, n, binary): a text log through text_index and
+    log_parse_text (n lines), a binary log (binlog_header says so) through binlog_index and
+    binlog_parse (n records).  The columns are None when n is 0.  A binary log whose record
+    walk stops before the end of the file raises MgenxError: a prefix is not analysed."""
+    import torch
+    dev = f"cuda:{eng.device}"
+    raw = np.frombuffer(bytes(log_bytes), np.uint8)
+    if is_binary_log(raw):
+        offs, info = binlog_index(raw)
+        if info.status != BINLOG_OK:
+            raise MgenxError(f"binary log: the record walk stopped with status "
+                             f"{_BINLOG_STATUS.get(info.status, info.status)} at offset "
+                             f"{int(info.consumed)} after {int(info.n_records)} records")
+        n = int(info.n_records)
+        if n == 0:
+            return None, 0, True
+        buf = torch.from_numpy(raw.copy()).to(dev)
+        rec_off = torch.from_numpy(offs.view(np.int64).copy()).to(dev)
+        return eng.binlog_parse(buf, rec_off, n), n, True
+    n = 0
+    if raw.size:
+        text = torch.from_numpy(raw.copy()).to(dev)
+        line_off, n = eng.text_index(text)
+    if n == 0:
+        return None, 0, False
+    return eng.log_parse_text(text, line_off, n, day_base=day_base), n, False
+
+
 def convert_binary_log(log, log_rx=True, flush=False, opts=0, device=0) -> tuple:
     """ConvertBinaryLog of a host binary log image on the GPU: (text bytes, BinlogInfo)."""
     import torch
@@ -1365,18 +1441,18 @@ def analyze_text_log(log_bytes, window=1.0, day_base=0, device=0) -> tuple:
     FindFlow -> MgenAnalytic::Update -> counters.  Returns (keys, counters, n_lines,
     n_malformed): numpy arrays of REPORT_KEY_DTYPE and FLOW_COUNTERS_DTYPE, one element per
     flow in the order of each flow's first RECV line.  The keys' protocol is that of the
-    first OK RECV line."""
+    first OK RECV line.  log_bytes may be a binary log (binlog_header says so): it is ingested by
+    binlog_index and binlog_parse instead, n_lines is then the record count and n_malformed the
+    MALFORMED records, and a log whose record walk stops early raises MgenxError.  The same holds
+    for every analyze_text_log_* and match_text_logs* helper."""
     import torch
     eng = Engine(device)
     table = None
     try:
-        dev = f"cuda:{device}"
-        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
-        line_off, n = eng.text_index(text)
+        p, n, _ = _ingest_log(eng, log_bytes, day_base)
         empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_COUNTERS_DTYPE))
         if n == 0:
             return empty + (0, 0)
-        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
         n_bad = int((p["status"] != PARSE_OK).sum().item())
         table = eng.flow_table(max(n, 16))
         flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
@@ -1439,13 +1515,10 @@ def analyze_text_log_clock(log_bytes, offset_only=False, day_base=0, device=0) -
     eng = Engine(device)
     table = None
     try:
-        dev = f"cuda:{device}"
-        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
-        line_off, n = eng.text_index(text)
+        p, n, _ = _ingest_log(eng, log_bytes, day_base)
         empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_CLOCK_DTYPE))
         if n == 0:
             return empty + (0, 0)
-        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
         n_bad = int((p["status"] != PARSE_OK).sum().item())
         table = eng.flow_table(max(n, 16))
         flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
@@ -1479,14 +1552,11 @@ def analyze_text_log_dist(log_bytes, permille=(500, 900, 990, 999), day_base=0,
     eng = Engine(device)
     table = None
     try:
-        dev = f"cuda:{device}"
-        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
-        line_off, n = eng.text_index(text)
+        p, n, _ = _ingest_log(eng, log_bytes, day_base)
         empty = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_DIST_DTYPE),
                  np.zeros((0, len(permille)), np.int64), np.zeros((0, FLOW_DIST_BINS), np.uint64))
         if n == 0:
             return empty + (0, 0)
-        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
         n_bad = int((p["status"] != PARSE_OK).sum().item())
         table = eng.flow_table(max(n, 16))
         flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
@@ -1533,9 +1603,7 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
     eng = Engine(device)
     table = None
     try:
-        dev = f"cuda:{device}"
-        text = torch.from_numpy(np.frombuffer(bytes(log_bytes), np.uint8).copy()).to(dev)
-        line_off, n = eng.text_index(text)
+        p, n, _ = _ingest_log(eng, log_bytes, day_base)
 
         def empty(n_lines, n_bad):
             r = (np.zeros(0, REPORT_KEY_DTYPE), np.zeros(0, FLOW_SERIES_STATE_DTYPE),
@@ -1546,7 +1614,6 @@ def analyze_text_log_series(log_bytes, width_us, t0_us=None, n_bins=None, day_ba
             return r
         if n == 0:
             return empty(0, 0)
-        p = eng.log_parse_text(text, line_off, n, day_base=day_base)
         n_bad = int((p["status"] != PARSE_OK).sum().item())
         table = eng.flow_table(max(n, 16))
         flow_idx, n_flows = eng.flow_lookup(table, p, p["src"], n)
@@ -1593,7 +1660,10 @@ def match_text_logs(send_log_bytes, recv_log_bytes, no_time=False, day_base=0, d
     and uint32 arrays with one element per line of the sender's log (the first two) and of the
     receiver's.  Flows are numbered by their first SEND line; the receiver-only flows follow
     from index n_send_flows.  The keys' source addresses are cleared (a SEND line has the port
-    only) and their protocol is that of the first OK SEND line."""
+    only) and their protocol is that of the first OK SEND line.  Either log may be a binary log.
+    A binary SEND record has no source port, so when the sender's log is binary the port is
+    cleared on both sides before the flows are looked up: flows that differ only in source port
+    merge.  match_text_logs_timeline and match_text_logs_multi do the same."""
     return _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, None)
 
 
@@ -1634,20 +1704,11 @@ def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins
     try:
         dev = f"cuda:{device}"
 
-        def side(log, want):
-            raw = np.frombuffer(bytes(log), np.uint8)
-            n = 0
-            if raw.size:
-                text = torch.from_numpy(raw.copy()).to(dev)
-                line_off, n = eng.text_index(text)
-            if n == 0:
-                return None, None, 0
-            p = eng.log_parse_text(text, line_off, n, day_base=day_base)
-            cols, src = eng.match_side(p, n, want)
-            return cols, src, n
+        def side(log, want, no_port=False):
+            return _match_side_of(eng, log, want, day_base, no_port)
 
-        s, s_src, ns = side(send_log, EVENT_SEND)
-        rsides = [side(log, EVENT_RECV) for log in recv_logs]
+        s, s_src, ns, s_bin = side(send_log, EVENT_SEND)
+        rsides = [side(log, EVENT_RECV, s_bin)[:3] for log in recv_logs]
         nr = sum(n for _, _, n in rsides)
         none = torch.zeros(0, dtype=torch.int32, device=dev)
         s_idx = none
@@ -1733,6 +1794,20 @@ def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins
         eng.close()
 
 
+def _match_side_of(eng, log, want, day_base, no_port):
+    """One log as a side of msg_match: (cols, src, n, binary) through _ingest_log and
+    match_side.  A binary log's SEND records have no source port (src reads port 0), so when
+    the sender's log is binary the port is cleared on both sides' src (no_port for the
+    receivers' logs): the flows then differ by flow id and destination only."""
+    p, n, binary = _ingest_log(eng, log, day_base)
+    if n == 0:
+        return None, None, 0, binary
+    cols, src = eng.match_side(p, n, want)
+    if no_port or (binary and want == EVENT_SEND):
+        src.view(-1, ADDR_DTYPE.itemsize)[:, 2:4] = 0
+    return cols, src, n, binary
+
+
 def _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, tl) -> tuple:
     import torch
     eng = Engine(device)
@@ -1740,20 +1815,11 @@ def _match_text_logs(send_log_bytes, recv_log_bytes, no_time, day_base, device, 
     try:
         dev = f"cuda:{device}"
 
-        def side(log, want):
-            raw = np.frombuffer(bytes(log), np.uint8)
-            n = 0
-            if raw.size:
-                text = torch.from_numpy(raw.copy()).to(dev)
-                line_off, n = eng.text_index(text)
-            if n == 0:
-                return None, None, 0
-            p = eng.log_parse_text(text, line_off, n, day_base=day_base)
-            cols, src = eng.match_side(p, n, want)
-            return cols, src, n
+        def side(log, want, no_port=False):
+            return _match_side_of(eng, log, want, day_base, no_port)
 
-        s, s_src, ns = side(send_log_bytes, EVENT_SEND)
-        r, r_src, nr = side(recv_log_bytes, EVENT_RECV)
+        s, s_src, ns, s_bin = side(send_log_bytes, EVENT_SEND)
+        r, r_src, nr, _ = side(recv_log_bytes, EVENT_RECV, s_bin)
         none = torch.zeros(0, dtype=torch.int32, device=dev)
         s_idx = r_idx = none
         nf = n_send = 0

@@ -2,7 +2,9 @@
 
     python -m mgen_amd.clock <log> [offset]
 
-reads a text log, fits on the GPU (analyze_text_log_clock: mgenx_flow_clock), per flow, the
+reads a text log or a binary log (`type=binary_log`: the helper tells them apart by the header
+line and ingests a binary log with mgenx_binlog_parse, so this tool needs no option for it), fits
+on the GPU (analyze_text_log_clock: mgenx_flow_clock), per flow, the
 straight line that lies under every (send time, latency) point and is closest to the points --
 the receiver clock's offset and skew plus the minimum path delay (Moon, Skelly, Towsley, INFOCOM
 1999) -- and prints one row per flow:

@@ -12,6 +12,11 @@ lost = sent - delivered is exact; lost_head + lost_tail is the part that no rece
 analysis can see.  Latencies are microseconds ("-" while nothing was delivered); the mean is the
 floor of lat_sum / delivered.  `notime` joins on (flow, seq) alone (MGENX_MATCH_NO_TIME): for
 SINK-sent logs, whose SEND stamp is the wall clock, and for logs whose time-stamp styles differ.
+
+Either log may be a binary log (`type=binary_log`): match_text_logs tells them apart by the header
+line and ingests a binary log with mgenx_binlog_parse, so this tool needs no option for it.  A
+binary SEND record holds no source port; with a binary sender's log the flows are keyed without
+it, so flows that differ only in source port merge.
 """
 from __future__ import annotations
 

@@ -3,8 +3,9 @@ multicast run.
 
     python -m mgen_amd.match_multi [-n] [-w WIDTH_SEC] <send.log> <recv1.log> [<recv2.log> ...]
 
-reads the sender's text log (SEND lines: `TXLOG`) and up to 64 receivers' logs (RECV lines),
-joins them on the GPU (match_text_logs_multi: mgenx_msg_match_multi) and prints one row per
+reads the sender's log (SEND lines: `TXLOG`) and up to 64 receivers' logs (RECV lines), each a
+text log or a binary log (told apart by the header line inside match_text_logs_multi: no option
+here; with a binary sender's log the flows are keyed without the source port), joins them on the GPU (match_text_logs_multi: mgenx_msg_match_multi) and prints one row per
 (flow, receiver), the receivers numbered from 0 in the order given:
 
     flow dst rcv sent delivered lost lost_head lost_tail rx_dup orphans lat_min lat_mean lat_max

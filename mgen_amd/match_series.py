@@ -3,7 +3,8 @@ load and exact loss per window of send time, or the list of outages.
 
     python -m mgen_amd.match_series [-r MIN] <send.log> <recv.log> <width_sec> [notime]
 
-reads the two text logs as `python -m mgen_amd.match` does and joins them on the GPU
+reads the two logs as `python -m mgen_amd.match` does (text or binary, told apart by the header
+line inside match_text_logs_timeline: no option here) and joins them on the GPU
 (match_text_logs_timeline: mgenx_msg_match_ex).  Without -r it writes, per flow, a comment line
 and one row per window of send time in which the flow sent something:
 

@@ -2,8 +2,10 @@
 
     python -m mgen_amd.series [-q 500,950,990] [-c fit|offset] <log> <width_sec> [outfile]
 
-reads a text log, reduces it on the GPU (analyze_text_log_series: mgenx_flow_series, one time
-axis for all flows) and writes, per flow, a comment line and one row per non-empty window:
+reads a text log or a binary log (`type=binary_log`: the helper tells them apart by the header
+line and ingests a binary log with mgenx_binlog_parse, so this tool needs no option for it),
+reduces it on the GPU (analyze_text_log_series: mgenx_flow_series, one time axis for all flows)
+and writes, per flow, a comment line and one row per non-empty window:
 
     # flow>1 src>10.0.0.1/5001 dst>10.0.0.9/5000
     bin_start_us n bytes fresh late advance lat_min lat_max lat_sum jitter_sum

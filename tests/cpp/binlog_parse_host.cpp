@@ -1,0 +1,80 @@
+// The binary log record decoder and the record walk's stop rule
+// (mgen_amd/csrc/mgenx_binlogparse.hpp) on the host.  Built with -fsanitize=address,undefined
+// (Makefile); each record is decoded from a heap copy of exactly its own bytes, placed at the
+// very end of the allocation, so a read past the record is reported by the sanitizer.
+//
+//   binlog_parse_host <file>
+// The file holds pieces, each a little-endian u32 byte count and then that many bytes (a
+// record, or a cut one: the count is the truth, not the record's own length field).
+// Output per piece (decimal unless noted):
+//   walk step event status protocol present rx_sec rx_usec tx_sec tx_usec flow seq size ttl
+//   flags err gps lat_raw lon_raw alt data_len src dst host data
+// where walk is the stop rule's verdict with the piece's bytes as all that is left of the file
+// (-1 go on, -2 end of file, else MGENX_BINLOG_*), an address is type:len:port:<32 hex digits>
+// and data is hex ("-" when empty).
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+
+#include "../../mgen_amd/csrc/mgenx_binlogparse.hpp"
+
+namespace bp = mgenx::bp;
+
+static void put_addr(const mgenx_addr& a) {
+  printf(" %u:%u:%u:", a.type, a.len, a.port);
+  for (int k = 0; k < 16; k++) printf("%02x", a.addr[k]);
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) {
+    fprintf(stderr, "usage: %s <pieces file>\n", argv[0]);
+    return 2;
+  }
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) {
+    perror(argv[1]);
+    return 2;
+  }
+  std::string in;
+  char chunk[65536];
+  size_t got;
+  while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) in.append(chunk, got);
+  fclose(f);
+  size_t at = 0;
+  while (at + 4 <= in.size()) {
+    uint32_t len;
+    memcpy(&len, in.data() + at, 4);
+    at += 4;
+    if (len > in.size() - at) {
+      fprintf(stderr, "piece at %zu runs past the file\n", at);
+      return 2;
+    }
+    uint8_t* rec = static_cast<uint8_t*>(malloc(len ? len : 1));  // exactly the piece: no slack
+    memcpy(rec, in.data() + at, len);
+    bp::View v;
+    v.lead = v.rec = rec;
+    v.n_lead = v.len = len;
+    uint32_t step = 0;
+    const int walk = bp::walk_step(v, len, &step);
+    bp::Rec r;
+    bp::decode_record(v, &r);
+    printf("%d %u %u %u %u %u %u %u %u %u %u %u %u %d %u %u %u %u %u %d %u", walk, step, r.event,
+           r.status, r.protocol, r.present, r.rx_sec, r.rx_usec, r.tx_sec, r.tx_usec, r.flow, r.seq,
+           r.size, r.ttl, r.flags, r.err, r.gps_status, r.lat_raw, r.lon_raw, r.alt, r.data_len);
+    put_addr(r.src);
+    put_addr(r.dst);
+    put_addr(r.host);
+    if (r.status == MGENX_PARSE_OK && r.data_len) {
+      printf(" ");
+      for (uint32_t k = 0; k < r.data_len; k++) printf("%02x", rec[r.data_pos + k]);
+    } else {
+      printf(" -");
+    }
+    printf("\n");
+    free(rec);
+    at += len;
+  }
+  return 0;
+}
