@@ -50,8 +50,10 @@ def walk_step(rec: bytes, avail=None):
     return WALK_NEXT, 4 + rl
 
 
-def _addr(atype, port, raw):
-    return atype, len(raw), port, bytes(raw) + bytes(16 - len(raw))
+def _addr(atype, alen, port, raw):
+    """An address of declared length alen whose bytes `raw` may have been cut short by the end
+    of the message: the length stays as declared, the missing bytes read as zero."""
+    return atype, alen, port, bytes(raw) + bytes(16 - len(raw))
 
 
 def _message(m: bytes, r: dict, recv: bool) -> bool:
@@ -63,7 +65,11 @@ def _message(m: bytes, r: dict, recv: bool) -> bool:
     if version != 2 or dtype not in ADDR_LEN or ADDR_LEN[dtype] != dlen:
         return False
     r["flow"], r["seq"], r["size"] = flow, seq, msg_len
-    r["dst"] = _addr(dtype, dport, m[24:24 + dlen])     # cut by the message's end
+    # Only the destination can be cut by the message's end (a 28-byte message holds 4 of an
+    # IPv6 destination's 16 bytes): Unpack keeps the declared length and zero fill.  The host
+    # address cannot (at + hlen > len(m) leaves the loop before it is read) and neither can
+    # the source (the walk rule wants 12 + its length inside the record).
+    r["dst"] = _addr(dtype, dlen, dport, m[24:24 + dlen])
     at = 24 + dlen
     gps, lat, lon, alt = 0, 10800000, 10800000, 0       # a fresh message: 0.0 degrees
     ptype, data = 0, b""
@@ -77,7 +83,7 @@ def _message(m: bytes, r: dict, recv: bool) -> bool:
         if htype in ADDR_LEN:
             if ADDR_LEN[htype] != hlen:
                 return False
-            r["host"] = _addr(htype, hport, m[at:at + hlen])
+            r["host"] = _addr(htype, hlen, hport, m[at:at + hlen])
             r["present"] |= R.HAS_HOST
         at += hlen
         if at + 13 > len(m):
@@ -127,7 +133,7 @@ def parse_record(rec: bytes) -> dict:
         r["protocol"] = proto if proto in (1, 2, 3) else 0
         if ADDR_LEN[atype] != alen:
             return r
-        r["src"] = _addr(atype, port, body[12:12 + alen])
+        r["src"] = _addr(atype, alen, port, body[12:12 + alen])
         if not _message(body[12 + alen:], r, True):
             return r
         r["status"], r["err"] = R.OK, 0

@@ -1,7 +1,9 @@
 // The binary log record decoder and the record walk's stop rule
 // (mgen_amd/csrc/mgenx_binlogparse.hpp) on the host.  Built with -fsanitize=address,undefined
 // (Makefile); each record is decoded from a heap copy of exactly its own bytes, placed at the
-// very end of the allocation, so a read past the record is reported by the sanitizer.
+// very end of the allocation, so a read past the record is reported by the sanitizer.  Each
+// piece is then decoded a second time through a split view (split_pass_agrees); a difference
+// names the piece on stderr and the program exits 1.
 //
 //   binlog_parse_host <file>
 // The file holds pieces, each a little-endian u32 byte count and then that many bytes (a
@@ -12,6 +14,7 @@
 // where walk is the stop rule's verdict with the piece's bytes as all that is left of the file
 // (-1 go on, -2 end of file, else MGENX_BINLOG_*), an address is type:len:port:<32 hex digits>
 // and data is hex ("-" when empty).
+#include <sanitizer/asan_interface.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,6 +28,36 @@ namespace bp = mgenx::bp;
 static void put_addr(const mgenx_addr& a) {
   printf(" %u:%u:%u:", a.type, a.len, a.port);
   for (int k = 0; k < 16; k++) printf("%02x", a.addr[k]);
+}
+
+// The piece once more through a view split the way the kernel splits it: `lead` a heap copy of
+// exactly the first min(len, kLead) bytes (at the very end of its allocation), `rec` a second
+// copy of the whole piece whose first n_lead bytes are poisoned.  A byte below n_lead read from
+// `rec`, or a byte at or past n_lead (or len) read from `lead`, is a sanitizer report; the walk
+// verdict, the step and every byte of the Rec must equal the whole-view pass.
+static bool split_pass_agrees(const uint8_t* whole, uint32_t len, int walk, uint32_t step,
+                              const bp::Rec& r) {
+  const uint32_t n_lead = len < bp::kLead ? len : bp::kLead;
+  uint8_t* lead = static_cast<uint8_t*>(malloc(n_lead ? n_lead : 1));
+  uint8_t* rec = static_cast<uint8_t*>(malloc(len ? len : 1));
+  memcpy(lead, whole, n_lead);
+  memcpy(rec, whole, len);
+  ASAN_POISON_MEMORY_REGION(rec, n_lead);
+  bp::View v;
+  v.lead = lead;
+  v.rec = rec;
+  v.n_lead = n_lead;
+  v.len = len;
+  uint32_t step2 = 0;
+  const int walk2 = bp::walk_step(v, len, &step2);
+  bp::Rec r2;
+  bp::decode_record(v, &r2);
+  ASAN_UNPOISON_MEMORY_REGION(rec, n_lead);
+  free(rec);
+  free(lead);
+  // Rec has no padding (rec_init writes its reserved members), so bytes compare the fields
+  static_assert(sizeof(bp::Rec) == 64 + 3 * sizeof(mgenx_addr), "padding in bp::Rec");
+  return walk2 == walk && step2 == step && memcmp(&r2, &r, sizeof r) == 0;
 }
 
 int main(int argc, char** argv) {
@@ -42,7 +75,7 @@ int main(int argc, char** argv) {
   size_t got;
   while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) in.append(chunk, got);
   fclose(f);
-  size_t at = 0;
+  size_t at = 0, piece = 0;
   while (at + 4 <= in.size()) {
     uint32_t len;
     memcpy(&len, in.data() + at, 4);
@@ -73,8 +106,13 @@ int main(int argc, char** argv) {
       printf(" -");
     }
     printf("\n");
+    if (!split_pass_agrees(rec, len, walk, step, r)) {
+      fprintf(stderr, "piece %zu (%u bytes): the split view decodes differently\n", piece, len);
+      return 1;
+    }
     free(rec);
     at += len;
+    piece++;
   }
   return 0;
 }

@@ -177,3 +177,31 @@ def test_convert_tcp_send_bounded_at_the_record(torch, oracle):
     assert len(lines) == 7
     assert b"host>" not in lines[0] and b"host>10.1.2.3/6000" in lines[-1], lines
     assert got == want, _diff(got, want)
+
+
+@pytest.mark.parametrize("opts", [0, 0x1])
+def test_convert_crafted_records(torch, oracle, opts):
+    """The records written byte by byte (binlog_cases: unknown host types with every length,
+    every cut of the stored message, type / length mismatches, edge values) convert like the
+    oracle's, byte for byte, and each record's text starts at its offset."""
+    import binlog_cases as C
+    import mgen_amd
+    recs = [rec for name, rec in C.crafted() if not name.startswith("too_long")]
+    log = B.binlog(recs)
+    want, st, n = oracle.convert_binary_log(log, opts=opts)
+    assert st == 0 and n == len(recs)
+    each = [oracle.convert_binary_log(B.binlog([rec]), opts=opts)[0] for rec in recs]
+    assert b"".join(each) == want and want.count(b"(invalid)") > 10
+    offs, info = mgen_amd.binlog_index(log)
+    assert info.status == 0 and info.n_records == n
+    eng = mgen_amd.Engine(0)
+    try:
+        buf = torch.from_numpy(np.frombuffer(log, np.uint8).copy()).cuda()
+        ro = torch.from_numpy(offs.view(np.int64).copy()).cuda()
+        text, pos = eng.convert_binary_log(buf, ro, n, 0, opts)
+        got = text.cpu().numpy().tobytes()
+        assert got == want, _diff(got, want)
+        starts = np.concatenate([[0], np.cumsum([len(t) for t in each])])
+        assert np.array_equal(pos.cpu().numpy(), starts)
+    finally:
+        eng.close()
