@@ -11,7 +11,8 @@ NAMES := mgenx_api mgenx_ctx mgenx_unpack mgenx_unpack_fixed mgenx_probe \
          mgenx_pack mgenx_scan mgenx_analytic mgenx_log mgenx_binlog mgenx_comm mgenx_worker \
          mgenx_worker_host mgenx_flowtab mgenx_tcp mgenx_rx mgenx_pcap mgenx_logparse \
          mgenx_flowdist mgenx_defrag mgenx_pcap_tcp mgenx_flowseries mgenx_match \
-         mgenx_flowquant mgenx_flowclock mgenx_matchmulti mgenx_binlogparse
+         mgenx_flowquant mgenx_flowclock mgenx_matchmulti mgenx_binlogparse \
+         mgenx_matchloss
 HDR := include/mgenx.h include/mgenx_diag.h mgen_amd/csrc/mgenx_common.hpp mgen_amd/csrc/mgenx_kernels.hpp \
        mgen_amd/csrc/mgenx_internal.hpp \
        mgen_amd/csrc/mgenx_unpack.hpp mgen_amd/csrc/mgenx_unpack_var.hpp \
@@ -31,7 +32,8 @@ all: mgen_amd/libmgenx.so mgen_amd/libmgenx_diag.so oracle tests/cpp/host_roundt
      tests/cpp/pcapng_host tests/cpp/flow_dist_host tests/cpp/pcap_tcp_host \
      tests/cpp/flow_series_host tests/cpp/msg_match_host tests/cpp/flow_quant_host \
      tests/cpp/flow_quant_arith_host tests/cpp/flow_clock_host tests/cpp/flow_clock_arith_host \
-     tests/cpp/match_timeline_host tests/cpp/msg_match_multi_host tests/cpp/binlog_parse_host
+     tests/cpp/match_timeline_host tests/cpp/msg_match_multi_host tests/cpp/binlog_parse_host \
+     tests/cpp/msg_match_multi_ex_host
 
 build/product/%.o: mgen_amd/csrc/%.hip $(HDR)
 	@mkdir -p build/product
@@ -151,6 +153,11 @@ tests/cpp/match_timeline_host: tests/cpp/match_timeline_host.cpp include/mgenx.h
 # mgenx::MessageMatchMulti::RunSeries (one sender, five receivers) against a serial loop in the
 # program
 tests/cpp/msg_match_multi_host: tests/cpp/msg_match_multi_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
+	$(HOSTCXX) $< -o $@ $(HOSTLD)
+
+# mgenx::MessageMatchMulti::RunLoss (one sender, three receivers: the loss runs, their list and
+# the pair matrix) against numbers worked out by hand in the program
+tests/cpp/msg_match_multi_ex_host: tests/cpp/msg_match_multi_ex_host.cpp include/mgenx.hpp include/mgenx.h mgen_amd/libmgenx.so
 	$(HOSTCXX) $< -o $@ $(HOSTLD)
 
 # mgenx::Pcap2Mgen with PcapOptions::tcp over a capture file (tests/test_gpu_pcap_tcp_cpp.py)

@@ -1702,8 +1702,8 @@ int mgenx_msg_match_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
  * popcount) and delivered_bytes (len x popcount); reached_any (popcount > 0), reached_all;
  * reach_min / reach_max, the least and greatest popcount (UINT64_MAX and 0 in an empty cell).
  *
- * There is no run list and there are no per-receiver loss runs: mgenx_msg_match_ex on one
- * receiver's records gives those.
+ * The loss runs per receiver, their list, and the loss that receivers share:
+ * mgenx_msg_match_multi_ex below.
  *
  * Asynchronous; ns == 0, nr == 0 and n_flows == 0 are legal.  The workspace is the context's,
  * shared with mgenx_msg_match (one stream at a time per context; it synchronises only to grow):
@@ -1745,6 +1745,86 @@ int mgenx_msg_match_multi(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                           struct mgenx_flow_fanout* dev_fanout,
                           struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
                           void* stream);
+
+/* ---- the same join, plus when each receiver was cut off and which receivers lose together ----
+ * mgenx_msg_match_multi_ex is mgenx_msg_match_multi (the same arguments, the same outputs, the
+ * same bytes) plus up to three optional parts, all in the terms above: counted record, identity,
+ * owner, send duplicate, delivered to r, send stamp, send-log order.  With lx == NULL, or with all
+ * three parts off, the call is mgenx_msg_match_multi: the same launches and the same bytes.  No
+ * reference code: this block is the contract.  Integer arithmetic only; every output byte is a
+ * function of the inputs alone; every output asked for is written on every call (no init call).
+ *
+ * For flow f let O_f[0 .. sent) be its owners in send-log order, the rank of an owner its
+ * position in that list, and D(k, r) = the owner of rank k was delivered to receiver r (bit r of
+ * its dev_send_mask).
+ *
+ * Run statistics (dev_rcv_runs non-null), dev_rcv_runs[f * n_rcv + r]: the runs of (f, r) are
+ * the maximal runs of consecutive ranks k with !D(k, r).  Send duplicates and skipped records are
+ * transparent, head and tail runs count, and a flow with sent > 0 that never reached r has one
+ * run of length sent.  loss_runs = their number, loss_run_max = the longest (0 when there is
+ * none), loss_run_hist[k] = the runs with min(floor(log2(length)), 17) == k.  The run lengths of a
+ * cell sum to sent - delivered, and the cell equals the loss_runs / loss_run_max / loss_run_hist
+ * that mgenx_msg_match leaves for flow f on the same send records and r's recv records alone.
+ *
+ * Run list (dev_n_runs non-null): one mgenx_rcv_loss_run per run of any (f, r) with
+ * length >= max(min_run, 1).  first_send / last_send are the send-record indices of the run's
+ * first and last undelivered owner (never a send duplicate next to it), t_first_us / t_last_us
+ * their send stamps, widened as mgenx_msg_match_ex states.  MGENX_RUN_HEAD: no owner of f before
+ * the run was delivered to r; MGENX_RUN_TAIL: none after it was (a cell never delivered has one
+ * run with both).  The order is by flow_idx, then last_send, then rcv; filtered to one receiver
+ * the list is mgenx_msg_match_ex's for that receiver's records, entry for entry, with rcv where
+ * that one has rsv.  dev_n_runs[0] = the number of such runs, always written;
+ * dev_runs[0 .. count) is written only when count <= run_cap, else not one byte of dev_runs
+ * changes (the two-pass convention of mgenx_msg_match_ex).
+ *
+ * Pair matrix (dev_pairs non-null), dev_pairs[(f * n_rcv + a) * n_rcv + b]: the span of (f, r)
+ * is the ranks from the owner dev_cells names first_send to the one it names last_send, ends
+ * included; empty when nothing was delivered to r.  The common span of (a, b) is the
+ * intersection of the two spans (empty when either is, or when they do not overlap), so that a
+ * late joiner's head loss and an early leaver's tail loss do not read as shared loss.  Over the
+ * owners k of the common span: span = their number, lost_a = those with !D(k, a), lost_b = those
+ * with !D(k, b), lost_both = those with neither.  An empty common span gives four zeros.  Entry
+ * (a, b)'s lost_a is entry (b, a)'s lost_b; on the diagonal span is the receiver's own span and
+ * the three loss fields equal the cell's sent - delivered - lost_head - lost_tail.
+ *
+ * Asynchronous; ns == 0, nr == 0 and n_flows == 0 are legal (with n_flows == 0 the three arrays
+ * may be null).  Beside mgenx_msg_match_multi's workspace the parts add, whichever of them are
+ * on, 20 bytes per send record, 4 (n_flows + 1), and 12 + 8 n_rcv bytes per 1024 send records
+ * (nothing per cell); the call synchronises only to grow the workspace.  MGENX_EINVAL, before
+ * any HIP call and with nothing written: whatever mgenx_msg_match_multi refuses; dev_pairs given
+ * with n_flows * n_rcv^2 >= 2^31; dev_n_runs given with a null dev_runs while run_cap > 0. */
+struct mgenx_rcv_runs {      /* 160 B; one per (flow, receiver) */
+  uint64_t loss_runs, loss_run_max, loss_run_hist[18];
+};
+struct mgenx_rcv_loss_run {  /* 40 B; mgenx_loss_run's layout with rcv where it has rsv */
+  uint32_t flow_idx, length;            /* undelivered owners in the run */
+  uint32_t first_send, last_send;       /* send-record indices of its first and last undelivered owner */
+  uint32_t flags, rcv;                  /* MGENX_RUN_*; the receiver */
+  int64_t  t_first_us, t_last_us;       /* the send stamps of first_send / last_send */
+};
+struct mgenx_rcv_pair {      /* 32 B; one per (flow, receiver a, receiver b) */
+  uint64_t span, lost_a, lost_b, lost_both;
+};
+typedef struct {             /* HOST struct; each of the three parts is optional */
+  struct mgenx_rcv_runs* dev_rcv_runs;        /* [n_flows * n_rcv]; null: not wanted */
+  uint32_t min_run, rsv;                      /* 0 is taken as 1 */
+  struct mgenx_rcv_loss_run* dev_runs; uint64_t run_cap;
+  uint64_t* dev_n_runs;                       /* null: no run list */
+  struct mgenx_rcv_pair* dev_pairs;           /* [n_flows * n_rcv * n_rcv]; null: not wanted */
+} mgenx_multi_loss;
+int mgenx_msg_match_multi_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                             const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                             const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len,
+                             uint32_t ns, const uint32_t* dev_recv_flow_idx,
+                             const uint32_t* dev_recv_seq, const uint32_t* dev_recv_tx_sec,
+                             const uint32_t* dev_recv_tx_usec, const uint32_t* dev_recv_rx_sec,
+                             const uint32_t* dev_recv_rx_usec, const uint32_t* dev_recv_rcv,
+                             uint32_t nr, uint32_t n_rcv, uint32_t n_flows, uint32_t opts,
+                             uint64_t* dev_send_mask, uint32_t* dev_recv_send,
+                             uint8_t* dev_recv_first, struct mgenx_rcv_cell* dev_cells,
+                             struct mgenx_flow_fanout* dev_fanout,
+                             struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
+                             const mgenx_multi_loss* lx, void* stream);
 
 /* ---- multi-GPU exchange (RCCL over xGMI) ----
  * One communicator per rank (one process per GPU): rank 0 calls mgenx_comm_unique_id and

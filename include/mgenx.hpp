@@ -948,6 +948,61 @@ class MessageMatchMulti {
   std::vector<Bin> Bins() { return Download(bins_, (size_t)n_flows_ * n_bins_); }  // row f = flow f
   std::vector<uint64_t> Outside() { return Download(outside_, n_bins_ ? n_flows_ : 0); }
 
+  // Run plus the three parts of mgenx_msg_match_multi_ex: the loss runs per (flow, receiver),
+  // the list of the runs of at least minRun lost messages (by flow, last send index, receiver)
+  // and the pair matrix.  The list is sized by a first call and the call is repeated once.
+  typedef struct mgenx_rcv_runs RcvRuns;
+  typedef struct mgenx_rcv_loss_run RcvLossRun;
+  typedef struct mgenx_rcv_pair RcvPair;
+  void RunLoss(const SendColumns& s, const RecvColumns& r, const std::vector<uint32_t>& rcv,
+               uint32_t minRun = 1) {
+    ns_ = (uint32_t)s.flow_idx.size();
+    nr_ = (uint32_t)r.flow_idx.size();
+    const std::vector<uint32_t>* sc[5] = {&s.flow_idx, &s.seq, &s.t_sec, &s.t_usec, &s.len};
+    const std::vector<uint32_t>* rc[7] = {&r.flow_idx, &r.seq,     &r.tx_sec, &r.tx_usec,
+                                          &r.rx_sec,   &r.rx_usec, &rcv};
+    hipStream_t st = ctx_.stream();
+    for (int k = 0; k < 5; k++) Upload(d_s_[k], *sc[k], ns_, st);
+    for (int k = 0; k < 7; k++) Upload(d_r_[k], *rc[k], nr_, st);
+    mask_.Resize(ns_);
+    rs_.Resize(nr_);
+    first_.Resize(nr_);
+    n_bins_ = 0;
+    bins_.Resize(0);
+    outside_.Resize(0);
+    rcv_runs_.Resize((size_t)n_flows_ * n_rcv_);
+    pairs_.Resize((size_t)n_flows_ * n_rcv_ * n_rcv_);
+    n_runs_dev_.Resize(1);
+    runs_.Resize(0);
+    n_runs_ = 0;
+    mgenx_multi_loss lx = {};
+    lx.dev_rcv_runs = rcv_runs_.data();
+    lx.min_run = minRun;
+    lx.dev_n_runs = n_runs_dev_.data();
+    lx.dev_pairs = pairs_.data();
+    for (int pass = 0; pass < 2; pass++) {
+      lx.dev_runs = runs_.data();
+      lx.run_cap = n_runs_;
+      ctx_.Check(mgenx_msg_match_multi_ex(
+                     ctx_.get(), d_s_[0].data(), d_s_[1].data(), d_s_[2].data(), d_s_[3].data(),
+                     d_s_[4].data(), ns_, d_r_[0].data(), d_r_[1].data(), d_r_[2].data(),
+                     d_r_[3].data(), d_r_[4].data(), d_r_[5].data(), d_r_[6].data(), nr_, n_rcv_,
+                     n_flows_, opts_, mask_.data(), rs_.data(), first_.data(), cells_.data(),
+                     fanout_.data(), stats_.data(), nullptr, &lx, st),
+                 "mgenx_msg_match_multi_ex");
+      if (pass) break;
+      n_runs_ = Download(n_runs_dev_, 1)[0];
+      if (n_runs_ == 0) break;
+      runs_.Resize((size_t)n_runs_);
+    }
+    ctx_.Sync();  // the host vectors are the caller's again
+  }
+  // row f, column r: element f * nRcv + r
+  std::vector<RcvRuns> RunStats() { return Download(rcv_runs_, (size_t)n_flows_ * n_rcv_); }
+  std::vector<RcvLossRun> LossRuns() { return Download(runs_, (size_t)n_runs_); }
+  // flow f, receivers a and b: element (f * nRcv + a) * nRcv + b
+  std::vector<RcvPair> Pairs() { return Download(pairs_, (size_t)n_flows_ * n_rcv_ * n_rcv_); }
+
  private:
   void Upload(DeviceArray<uint32_t>& d, const std::vector<uint32_t>& h, uint32_t n,
               hipStream_t st) {
@@ -973,6 +1028,11 @@ class MessageMatchMulti {
   DeviceArray<uint64_t> mask_, outside_;
   DeviceArray<uint8_t> first_;
   DeviceArray<Bin> bins_;
+  uint64_t n_runs_ = 0;
+  DeviceArray<RcvRuns> rcv_runs_;
+  DeviceArray<RcvLossRun> runs_;
+  DeviceArray<RcvPair> pairs_;
+  DeviceArray<uint64_t> n_runs_dev_;
 };
 
 // ---- per-flow clock offset and skew removal ------------------------------------------------

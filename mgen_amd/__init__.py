@@ -36,6 +36,7 @@ from ._abi import (  # noqa: F401
     BINLOG_OK, BINLOG_HEADER, BINLOG_TOO_LONG, BINLOG_EVENT, BINLOG_SHORT,
     CLOCK_NONE, CLOCK_OFFSET_ONLY, FLOW_CLOCK_DTYPE,
     MATCH_MAX_RCV, RCV_CELL_DTYPE, FLOW_FANOUT_DTYPE, MULTI_BIN_DTYPE, MultiTimeline,
+    RCV_RUNS_DTYPE, RCV_LOSS_RUN_DTYPE, RCV_PAIR_DTYPE, MultiLoss,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "mgenx_pcap_tcp", "mgenx_pcapng_tcp", "mgenx_tcp_frame",
     "mgenx_match_side", "mgenx_msg_match", "mgenx_flow_clock", "mgenx_msg_match_ex",
     "mgenx_msg_match_multi", "mgenx_binlog_header", "mgenx_binlog_parse",
+    "mgenx_msg_match_multi_ex",
 )
 DIAG_SYMBOLS = ("mgenx_set_tuning", "mgenx_diag_stream_read", "mgenx_diag_group_rw",
                 "mgenx_diag_seg_prof", "mgenx_diag_stream_read_w", "mgenx_diag_worker_stamps",
@@ -193,6 +195,10 @@ def load(diag: bool = False):
                                      P, P, P, ctypes.POINTER(MatchTimeline), P]
     L.mgenx_msg_match_multi.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, P, u32, u32, u32,
                                         u32, P, P, P, P, P, P, ctypes.POINTER(MultiTimeline), P]
+    L.mgenx_msg_match_multi_ex.argtypes = [P, P, P, P, P, P, u32, P, P, P, P, P, P, P, u32, u32,
+                                           u32, u32, P, P, P, P, P, P,
+                                           ctypes.POINTER(MultiTimeline),
+                                           ctypes.POINTER(MultiLoss), P]
     L.mgenx_flow_dist_bin.argtypes = [u64]
     L.mgenx_flow_dist_bin.restype = u32
     L.mgenx_flow_dist_bin_lo.argtypes = [u32]
@@ -859,6 +865,75 @@ class Engine:
         if timeline is not None:
             res += (bins[:n_flows * n_bins * MULTI_BIN_DTYPE.itemsize], outside[:n_flows])
         return res
+
+    def msg_match_multi_loss(self, n_flows, n_rcv, send, recv, *, run_stats=True, min_run=1,
+                             pairs=True, opts=0, timeline=None, ns=None, nr=None):
+        """msg_match_multi plus the parts of mgenx_msg_match_multi_ex.  Returns msg_match_multi's
+        tuple (six tensors, eight with a timeline) followed by (rcv_runs, runs, pairs): uint8 tensors of n_flows x n_rcv x 160 B
+        (RCV_RUNS_DTYPE; None unless run_stats), n_runs x 40 B (RCV_LOSS_RUN_DTYPE: the runs of
+        at least min_run lost messages by flow, last send index and receiver; None when min_run
+        is None) and n_flows x n_rcv x n_rcv x 32 B (RCV_PAIR_DTYPE; None unless pairs).  The run
+        list is sized by a first call and the call is repeated once (one read-back)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        ns = send["flow_idx"].numel() if ns is None else ns
+        nr = recv["flow_idx"].numel() if nr is None else nr
+        mask = torch.empty(max(ns, 1), dtype=torch.int64, device=dev)
+        rs = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(max(nr, 1), dtype=torch.uint8, device=dev)
+        n_cells = n_flows * n_rcv
+        cells = torch.empty(max(n_cells, 1) * RCV_CELL_DTYPE.itemsize, dtype=torch.uint8,
+                            device=dev)
+        fanout = torch.empty(max(n_flows, 1) * FLOW_FANOUT_DTYPE.itemsize, dtype=torch.uint8,
+                             device=dev)
+        stats = torch.empty(MATCH_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        tl, n_bins = None, 0
+        if timeline is not None:
+            t0_us, width_us, n_bins = (int(v) for v in timeline)
+            bins = torch.empty(max(n_flows * n_bins, 1) * MULTI_BIN_DTYPE.itemsize,
+                               dtype=torch.uint8, device=dev)
+            outside = torch.zeros(max(n_flows, 1), dtype=torch.int64, device=dev)
+            tl = ctypes.byref(MultiTimeline(t0_us=t0_us, width_us=width_us, n_bins=n_bins,
+                                            dev_bins=bins.data_ptr(),
+                                            dev_outside=outside.data_ptr()))
+        lx = MultiLoss(min_run=0 if min_run is None else int(min_run), run_cap=0)
+        rcv_runs = runs = pair = n_runs = None
+        if run_stats:
+            rcv_runs = torch.empty(max(n_cells, 1) * RCV_RUNS_DTYPE.itemsize, dtype=torch.uint8,
+                                   device=dev)
+            lx.dev_rcv_runs = rcv_runs.data_ptr()
+        if pairs:
+            pair = torch.empty(max(n_cells * n_rcv, 1) * RCV_PAIR_DTYPE.itemsize,
+                               dtype=torch.uint8, device=dev)
+            lx.dev_pairs = pair.data_ptr()
+        if min_run is not None:
+            n_runs = torch.zeros(1, dtype=torch.int64, device=dev)
+            runs = torch.empty(0, dtype=torch.uint8, device=dev)
+            lx.dev_n_runs = n_runs.data_ptr()
+        for again in (False, True):
+            self._check(self.lib.mgenx_msg_match_multi_ex(
+                self.ctx, _ptr(send["flow_idx"]), _ptr(send["seq"]), _ptr(send["t_sec"]),
+                _ptr(send["t_usec"]), _ptr(send["len"]), ns, _ptr(recv["flow_idx"]),
+                _ptr(recv["seq"]), _ptr(recv["tx_sec"]), _ptr(recv["tx_usec"]),
+                _ptr(recv["rx_sec"]), _ptr(recv["rx_usec"]), _ptr(recv["rcv"]), nr, n_rcv,
+                n_flows, opts, _ptr(mask), _ptr(rs), _ptr(first), _ptr(cells), _ptr(fanout),
+                _ptr(stats), tl, ctypes.byref(lx), _stream(self.device)),
+                "mgenx_msg_match_multi_ex")
+            if again or n_runs is None:
+                break
+            count = int(n_runs.item())
+            if count == 0:
+                break
+            runs = torch.empty(count * RCV_LOSS_RUN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            lx.dev_runs, lx.run_cap = runs.data_ptr(), count
+        res = (mask[:ns], rs[:nr], first[:nr], cells[:n_cells * RCV_CELL_DTYPE.itemsize],
+               fanout[:n_flows * FLOW_FANOUT_DTYPE.itemsize], stats)
+        if timeline is not None:
+            res += (bins[:n_flows * n_bins * MULTI_BIN_DTYPE.itemsize], outside[:n_flows])
+        return res + (
+                None if rcv_runs is None else rcv_runs[:n_cells * RCV_RUNS_DTYPE.itemsize],
+                runs,
+                None if pair is None else pair[:n_cells * n_rcv * RCV_PAIR_DTYPE.itemsize])
 
     def msg_match_timeline(self, n_flows, send, recv, t0_us, width_us, n_bins, *, min_run=1,
                            opts=0, ns=None, nr=None):
@@ -1682,7 +1757,8 @@ def match_text_logs_timeline(send_log, recv_log, width_us, t0_us=None, n_bins=No
 
 
 def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins=None,
-                          no_time=False, day_base=0, device=0) -> tuple:
+                          no_time=False, day_base=0, device=0, min_run=None,
+                          pairs=False) -> tuple:
     """A sender's text log (SEND lines) joined with the text logs of several receivers (RECV
     lines) on the GPU: every log goes through line index -> parse -> match_side, FindFlow runs
     on one table (sender first, then the receivers in the order given), the receivers' columns
@@ -1693,7 +1769,13 @@ def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins
     message reached receiver r), and the number of flows the sender's log has (receiver-only
     flows follow).  With width_us also (bins, outside, t0_us): MULTI_BIN_DTYPE [n_flows, n_bins]
     over windows of send time, uint64 [n_flows], and the first window's start; by default t0_us
-    is the lowest SEND stamp and n_bins just enough for the highest."""
+    is the lowest SEND stamp and n_bins just enough for the highest.
+    With min_run (an int; 0 is taken as 1) or pairs=True the join is mgenx_msg_match_multi_ex and
+    the tuple goes on, after whatever stands above, with: for min_run (rcv_runs, runs),
+    RCV_RUNS_DTYPE [n_flows, n_rcv] and RCV_LOSS_RUN_DTYPE (the runs of at least min_run lost
+    messages by flow, last send index and receiver; first_send / last_send are 0-based lines of
+    the sender's log); then for pairs RCV_PAIR_DTYPE [n_flows, n_rcv, n_rcv].  Without them the
+    call returns exactly what it returned before they existed."""
     import torch
     recv_logs = list(recv_logs)
     n_rcv = len(recv_logs)
@@ -1765,8 +1847,14 @@ def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins
                     n_bins = max((hi - int(t0_us)) // width_us + 1, 1)
             t0_us, n_bins = int(t0_us), int(n_bins)
             timeline = (t0_us, width_us, n_bins)
-        out = eng.msg_match_multi(nf, n_rcv, send, recv, opts=opts, timeline=timeline, ns=ns,
-                                  nr=nr)
+        loss = min_run is not None or pairs
+        if loss:
+            out = eng.msg_match_multi_loss(nf, n_rcv, send, recv, run_stats=min_run is not None,
+                                           min_run=min_run, pairs=pairs, opts=opts,
+                                           timeline=timeline, ns=ns, nr=nr)
+        else:
+            out = eng.msg_match_multi(nf, n_rcv, send, recv, opts=opts, timeline=timeline, ns=ns,
+                                      nr=nr)
         mask, _rs, _first, cells, fanout, stats = out[:6]
         keys = np.zeros(0, REPORT_KEY_DTYPE)
         if nf:
@@ -1787,6 +1875,11 @@ def match_text_logs_multi(send_log, recv_logs, width_us=None, t0_us=None, n_bins
         if timeline is not None:
             res += (out[6].cpu().numpy().view(MULTI_BIN_DTYPE).reshape(nf, n_bins).copy(),
                     out[7].cpu().numpy().view(np.uint64).copy(), t0_us)
+        if min_run is not None:
+            res += (out[-3].cpu().numpy().view(RCV_RUNS_DTYPE).reshape(nf, n_rcv).copy(),
+                    out[-2].cpu().numpy().view(RCV_LOSS_RUN_DTYPE).copy())
+        if pairs:
+            res += (out[-1].cpu().numpy().view(RCV_PAIR_DTYPE).reshape(nf, n_rcv, n_rcv).copy(),)
         return res
     finally:
         if table is not None:

@@ -213,6 +213,25 @@ class MultiTimeline(ctypes.Structure):   # mgenx_multi_timeline (a host struct)
                 ("dev_outside", ctypes.c_void_p)]
 
 
+# mgenx_msg_match_multi_ex: struct mgenx_rcv_runs, struct mgenx_rcv_loss_run, struct mgenx_rcv_pair
+RCV_RUNS_DTYPE = np.dtype([
+    ("loss_runs", "<u8"), ("loss_run_max", "<u8"), ("loss_run_hist", "<u8", (MATCH_RUN_BINS,))])
+RCV_LOSS_RUN_DTYPE = np.dtype([
+    ("flow_idx", "<u4"), ("length", "<u4"), ("first_send", "<u4"), ("last_send", "<u4"),
+    ("flags", "<u4"), ("rcv", "<u4"), ("t_first_us", "<i8"), ("t_last_us", "<i8")])
+RCV_PAIR_DTYPE = np.dtype([
+    ("span", "<u8"), ("lost_a", "<u8"), ("lost_b", "<u8"), ("lost_both", "<u8")])
+assert (RCV_RUNS_DTYPE.itemsize, RCV_LOSS_RUN_DTYPE.itemsize, RCV_PAIR_DTYPE.itemsize) == \
+    (160, 40, 32)
+
+
+class MultiLoss(ctypes.Structure):   # mgenx_multi_loss (a host struct)
+    _fields_ = [("dev_rcv_runs", ctypes.c_void_p), ("min_run", ctypes.c_uint32),
+                ("rsv", ctypes.c_uint32), ("dev_runs", ctypes.c_void_p),
+                ("run_cap", ctypes.c_uint64), ("dev_n_runs", ctypes.c_void_p),
+                ("dev_pairs", ctypes.c_void_p)]
+
+
 # ---- per-flow clock offset and skew (mgenx_flow_clock, include/mgenx.h) ----
 CLOCK_NONE = 0xFFFFFFFF     # MGENX_CLOCK_NONE
 CLOCK_OFFSET_ONLY = 0x1     # MGENX_CLOCK_OFFSET_ONLY

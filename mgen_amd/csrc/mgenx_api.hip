@@ -488,6 +488,33 @@ int mgenx_msg_match_multi(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                           struct mgenx_flow_fanout* dev_fanout,
                           struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
                           void* stream) {
+  return mgenx_msg_match_multi_ex(ctx, dev_send_flow_idx, dev_send_seq, dev_send_t_sec,
+                                  dev_send_t_usec, dev_send_len, ns, dev_recv_flow_idx,
+                                  dev_recv_seq, dev_recv_tx_sec, dev_recv_tx_usec, dev_recv_rx_sec,
+                                  dev_recv_rx_usec, dev_recv_rcv, nr, n_rcv, n_flows, opts,
+                                  dev_send_mask, dev_recv_send, dev_recv_first, dev_cells,
+                                  dev_fanout, dev_stats, tl, nullptr, stream);
+}
+
+int mgenx_msg_match_multi_ex(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
+                             const uint32_t* dev_send_seq, const uint32_t* dev_send_t_sec,
+                             const uint32_t* dev_send_t_usec, const uint32_t* dev_send_len,
+                             uint32_t ns, const uint32_t* dev_recv_flow_idx,
+                             const uint32_t* dev_recv_seq, const uint32_t* dev_recv_tx_sec,
+                             const uint32_t* dev_recv_tx_usec, const uint32_t* dev_recv_rx_sec,
+                             const uint32_t* dev_recv_rx_usec, const uint32_t* dev_recv_rcv,
+                             uint32_t nr, uint32_t n_rcv, uint32_t n_flows, uint32_t opts,
+                             uint64_t* dev_send_mask, uint32_t* dev_recv_send,
+                             uint8_t* dev_recv_first, struct mgenx_rcv_cell* dev_cells,
+                             struct mgenx_flow_fanout* dev_fanout,
+                             struct mgenx_match_stats* dev_stats, const mgenx_multi_timeline* tl,
+                             const mgenx_multi_loss* lx, void* stream) {
+  if (lx) {
+    if (lx->dev_pairs && n_rcv >= 1u && n_rcv <= 64u &&
+        (uint64_t)n_flows * n_rcv * n_rcv >= (1ull << 31))
+      return MGENX_EINVAL;
+    if (lx->dev_n_runs && !lx->dev_runs && lx->run_cap > 0) return MGENX_EINVAL;
+  }
   if (!ctx || !dev_stats || n_rcv < 1u || n_rcv > 64u || ns > (1u << 30) || nr > (1u << 30) ||
       (uint64_t)n_flows * n_rcv >= (1ull << 31))
     return MGENX_EINVAL;
@@ -512,7 +539,7 @@ int mgenx_msg_match_multi(mgenx_ctx* ctx, const uint32_t* dev_send_flow_idx,
                                    dev_recv_seq, dev_recv_tx_sec, dev_recv_tx_usec,
                                    dev_recv_rx_sec, dev_recv_rx_usec, dev_recv_rcv, nr, n_rcv,
                                    n_flows, opts, dev_send_mask, dev_recv_send, dev_recv_first,
-                                   dev_cells, dev_fanout, dev_stats, tl, (hipStream_t)stream,
+                                   dev_cells, dev_fanout, dev_stats, tl, lx, (hipStream_t)stream,
                                    ctx->err, sizeof(ctx->err));
 }
 

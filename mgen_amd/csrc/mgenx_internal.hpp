@@ -251,8 +251,24 @@ int msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_t* s_se
                         uint32_t n_flows, uint32_t opts, uint64_t* send_mask, uint32_t* recv_send,
                         uint8_t* recv_first, struct mgenx_rcv_cell* cells,
                         struct mgenx_flow_fanout* fanout, struct mgenx_match_stats* stats,
-                        const mgenx_multi_timeline* tl, hipStream_t stream, char* err,
-                        size_t errn);
+                        const mgenx_multi_timeline* tl, const mgenx_multi_loss* lx,
+                        hipStream_t stream, char* err, size_t errn);
+// mgenx_matchloss.hip: the loss runs and the pair matrix of mgenx_msg_match_multi_ex, run by
+// msg_match_multi_run after its main pass on what the join holds by then.  lx has at least one
+// part on.  mem: multi_loss_ws(ns, n_flows, n_rcv) bytes of device memory, 256-B aligned; its
+// first piece, multi_loss_rank(mem), takes every owner's rank per sorted position (ns words).
+// account false (no send record or no flow): only the empty values are written.
+struct MultiLossIn {
+  const uint32_t *keys, *order, *bnd, *own;   // flow_sort_run's and match_mark_kernel's
+  const uint64_t *send_mask, *minp, *maxp;    // [ns], [n_cells], [n_cells]
+  const struct mgenx_flow_fanout* fanout;     // sent complete
+  const uint32_t *t_sec, *t_usec;             // the send stamps
+  uint32_t ns, n_flows, n_rcv;
+};
+size_t multi_loss_ws(uint32_t ns, uint32_t n_flows, uint32_t n_rcv);
+uint32_t* multi_loss_rank(void* mem);
+int multi_loss_run(void* mem, const MultiLossIn& in, const mgenx_multi_loss* lx, bool account,
+                   hipStream_t stream, char* err, size_t errn);
 
 // ---- mgenx_log.hip ----
 mgenx_log_ws* log_ws_new();

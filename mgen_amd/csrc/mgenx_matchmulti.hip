@@ -27,7 +27,10 @@
 //      per value, kept the same way, so no array is indexed at run time; the sums go out once
 //      per wave and flow.  multi_series_kernel reduces the owners of one (flow, window) per wave;
 //   5. multi_finish_kernel: a lane per cell turns the two packed words into lost_head,
-//      lost_tail, first_send, last_send.
+//      lost_tail, first_send, last_send;
+//   6. mgenx_msg_match_multi_ex only: multi_main_kernel also leaves every owner's rank per sorted
+//      position, and mgenx_matchloss.hip's passes (multi_loss_run) follow: the loss runs per
+//      (flow, receiver), their list, and the loss that pairs of receivers share.
 // Integer sums, minima, maxima and ORs commute: the bytes left do not depend on the order the
 // workgroups finish in.
 #include <stdio.h>
@@ -274,7 +277,8 @@ multi_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
                   const uint32_t* __restrict__ bnd, uint32_t n_flows, uint32_t n_rcv,
                   const uint32_t* __restrict__ own, const uint64_t* __restrict__ send_mask,
                   const uint32_t* __restrict__ send_len, const uint32_t* __restrict__ carry,
-                  uint64_t* minp, uint64_t* maxp, FlowFanout* fanout) {
+                  uint64_t* minp, uint64_t* maxp, FlowFanout* fanout,
+                  uint32_t* __restrict__ rank_out) {
   __shared__ uint32_t s_v[kWaves], s_h[kWaves];
   const uint32_t c = blockIdx.x, t = threadIdx.x;
   const uint32_t nv = bnd[n_flows];
@@ -302,6 +306,7 @@ multi_main_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict_
   const uint32_t incl = seg_scan<SumOp>(v, head, s_v, s_h);
   // the owner's rank among its flow's owners, and the word the cells keep
   const uint64_t pk = ((uint64_t)(incl - (owner ? 1u : 0u)) << 32) | i;
+  if (rank_out && owner) rank_out[p] = incl - 1u;  // (mgenx_msg_match_multi_ex's passes read it)
   const uint32_t pc = (uint32_t)__popcll(m);
 
   const uint32_t lane = t & 63u;
@@ -459,8 +464,12 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
                                uint64_t* send_mask, uint32_t* recv_send, uint8_t* recv_first,
                                struct mgenx_rcv_cell* cells, struct mgenx_flow_fanout* fanout,
                                struct mgenx_match_stats* stats, const mgenx_multi_timeline* tl,
-                               hipStream_t stream, char* err, size_t errn) {
+                               const mgenx_multi_loss* lx, hipStream_t stream, char* err,
+                               size_t errn) {
   const bool series = tl && tl->n_bins > 0 && n_flows > 0;
+  // mgenx_msg_match_multi_ex's parts; with none of them the launches and the bytes are
+  // mgenx_msg_match_multi's
+  const bool loss = lx && (lx->dev_rcv_runs || lx->dev_n_runs || lx->dev_pairs);
   uint32_t n_slots = 64, n_pairs = 64;  // powers of two >= 2 ns, 2 nr
   while (n_slots < 2u * ns) n_slots <<= 1;
   while (n_pairs < 2u * nr) n_pairs <<= 1;
@@ -471,7 +480,8 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
                own_b = a256((size_t)ns * 4u),
                sort_b = account ? a256(mgenx::flow_sort_ws(ns, n_flows)) : 0,
                cell_b = a256((size_t)n_cells * 8u), c4 = a256((size_t)n_chunks * 4u);
-  const size_t need = tab_b + pair_b + own_b + sort_b + 2 * cell_b + 3 * c4;
+  const size_t loss_b = loss ? a256(mgenx::multi_loss_ws(ns, n_flows, n_rcv)) : 0;
+  const size_t need = tab_b + pair_b + own_b + sort_b + 2 * cell_b + 3 * c4 + loss_b;
   if (ws.reserve(need) != hipSuccess) {
     snprintf(err, errn, "msg_match_multi: workspace of %zu bytes", need);
     return MGENX_EDEVICE;
@@ -486,6 +496,7 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
   uint32_t* trail = (uint32_t*)take(c4);
   uint32_t* has_head = (uint32_t*)take(c4);
   uint32_t* carry = (uint32_t*)take(c4);
+  void* loss_mem = take(loss_b);
 
   const bool use_time = !(opts & MGENX_MATCH_NO_TIME);
   const uint32_t mask = n_slots - 1u, pmask = n_pairs - 1u;
@@ -516,7 +527,19 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
     snprintf(err, errn, "msg_match_multi: %s", hipGetErrorString(e));
     return MGENX_EDEVICE;
   }
-  if (!account) return MGENX_OK;  // (no owner: the empty values are the result)
+  mgenx::MultiLossIn lin = {};
+  lin.own = own;
+  lin.send_mask = send_mask;
+  lin.minp = minp;
+  lin.maxp = maxp;
+  lin.fanout = fanout;
+  lin.t_sec = s_sec;
+  lin.t_usec = s_usec;
+  lin.ns = ns;
+  lin.n_flows = n_flows;
+  lin.n_rcv = n_rcv;
+  if (!account)  // (no owner: the empty values are the result)
+    return loss ? mgenx::multi_loss_run(loss_mem, lin, lx, false, stream, err, errn) : MGENX_OK;
   const uint32_t *keys, *order, *bnd;
   const int rc = mgenx::flow_sort_run(sort_mem, s_flow, ns, n_flows, &keys, &order, &bnd, stream,
                                      err, errn);
@@ -526,7 +549,8 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
   hipLaunchKernelGGL(match_carry_kernel, dim3(1), dim3(kChunk), 0, stream, trail, has_head,
                      n_chunks, carry);
   hipLaunchKernelGGL(multi_main_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, order, bnd,
-                     n_flows, n_rcv, own, send_mask, s_len, carry, minp, maxp, fanout);
+                     n_flows, n_rcv, own, send_mask, s_len, carry, minp, maxp, fanout,
+                     loss ? mgenx::multi_loss_rank(loss_mem) : (uint32_t*)nullptr);
   if (series)
     hipLaunchKernelGGL(multi_series_kernel, dim3(n_chunks), dim3(kChunk), 0, stream, keys, order,
                        bnd, n_flows, n_rcv, own, send_mask, s_len, s_sec, s_usec, tl->t0_us,
@@ -537,6 +561,12 @@ int mgenx::msg_match_multi_run(DevBuf& ws, const uint32_t* s_flow, const uint32_
   if (e != hipSuccess) {
     snprintf(err, errn, "msg_match_multi: %s", hipGetErrorString(e));
     return MGENX_EDEVICE;
+  }
+  if (loss) {
+    lin.keys = keys;
+    lin.order = order;
+    lin.bnd = bnd;
+    return mgenx::multi_loss_run(loss_mem, lin, lx, true, stream, err, errn);
   }
   return MGENX_OK;
 }
